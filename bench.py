@@ -4,8 +4,15 @@ layers (BASELINE.json).  One step = one pass of the hot path (MSDeformAttn pixel
 hypersphere transformer decoder -> instance post-processing) over one batch of 8 synthetic frames'
 backbone features that are already resident in HBM.  Backbone excluded.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
+* A plain run sets up, warms up (W steps), times exactly K steps, writes the last step's outputs when ``--dump-outputs DIR`` is
+  given and prints the line: `value` (images/s), `ms_per_step` (one timed step), `steps` = K.
+* ``--dump-outputs DIR``: what the timed path returned for its last step (scores, classes, boxes, query indices, a fixed seeded
+  sample of the masks and every mask's area) as DIR/<name>.npy in float32 / float64.  The inputs are seeded: two builds run with
+  the same arguments can be compared output for output.
+* ``--full`` adds everything beyond the headline figure, listed below: the one-batch-in-flight figure, per-kernel timings and
+  rooflines, the 16-bit plans (configs[2]), the mean-shift unit, configs[1..4] sub-results and the CPU baseline.
 * ``--gpus N`` (N > 1) launched WITHOUT torch.distributed.run starts the N ranks itself (one process per GPU,
   LOCAL_RANK = device index, rendezvous on 127.0.0.1) -- the reference starts its N workers from one command the same way
   (MSMFormer/tabletop_train_net_pretrained.py:326-336).  Under ``python -m torch.distributed.run --nproc-per-node N ...
@@ -13,22 +20,22 @@ backbone features that are already resident in HBM.  Backbone excluded (SURVEY.m
 * Weak scaling: every rank processes its own batches of 8 images (independent units, no data-path collective); ranks
   exchange one small metrics record (images, elapsed, checksum) by all_gather after the timed region.
 * Throughput mode by default: ``--inflight`` (4) batches of 8 are in flight at a time, each replayed from its own HIP graph
-  on its own stream (graphs.PipelinedInference).  The JSON line also carries the figure with ONE batch in flight
+  on its own stream (graphs.PipelinedInference).  Under ``--full`` the JSON line also carries the figure with ONE batch in flight
   (``one_batch_in_flight``); ``--inflight 1`` times only that.
-* The timed region is at least ``--min-seconds`` (1 s) long: when K steps would be shorter, more steps are timed and
-  ``steps`` reports the number actually timed (``steps_requested`` = K).
-* ``roofline``: the dominant kernel of the step by time, the fused encoder-layer tail (msm_encoder_block_fwd): FLOPs it executes /
+* The headline times exactly K steps (``steps`` = ``steps_requested`` = K).  Under ``--full`` the one-batch figure and the precision legs
+  time at least ``--min-seconds`` (1 s) each.
+* ``roofline`` (``--full``): the dominant kernel of the step by time, the fused encoder-layer tail (msm_encoder_block_fwd): FLOPs it executes /
   its mean launch duration (HIP events around graph replays of the step's six launches) / the fp32 MFMA peak, PMC traffic from
   profiles/step_traffic.json.  ``roofline.mask_step``: the Q x pixel-embedding mask step the metric names -- the full-resolution
   kernel characterised per launch, and what the default plan runs for the ten predictions (one full-resolution launch + nine at
   key resolution) with executed and reference FLOPs side by side.
-* N = 1 adds, on rank 0: ``kernels`` (event-timed per entry point of one eager pass), ``mean_shift`` (the classic UCN
+* ``--full`` with N = 1 adds, on rank 0: ``kernels`` (event-timed per entry point of one eager pass), ``mean_shift`` (the classic UCN
   clustering unit with its own roofline entries), ``configs`` (BASELINE configs[2] slice / [3] / [4] timed by this run)
   and ``cpu_baseline`` (the oracle on the host cores).
 
 Prints ONE JSON line on rank 0, at most 8000 bytes (compact_line): the contract's keys, a flat `roofline` and `cpu_baseline`, a short
-`collective` and `summary`.  The full document (`kernels`, `configs`, `mean_shift`, per-rank detail) is written to
-gpurun_out/bench_full.json (--detail).
+`collective` and `summary`.  Under ``--full`` the full document (`kernels`, `configs`, `mean_shift`, per-rank detail) is written to
+bench_out/bench_full.json (--detail).
 """
 import argparse
 import json
@@ -940,7 +947,7 @@ def build_summary(result):
     ~20 KB): per config the throughput `v` (images/s unless noted), the one-batch-in-flight step `ms1`, the dtype `dt` and the
     roofline fraction `rf` of that config's dominant kernel.  Every number README / DESIGN quote is here or in `roofline`."""
     cfg = result.get("configs") or {}
-    r = result["roofline"]
+    r = result.get("roofline") or {}                  # (empty in a plain run: the roofline legs are --full's)
 
     def pick(d, *path, nd=1):
         for k in path:
@@ -950,7 +957,7 @@ def build_summary(result):
         return round(d, nd) if isinstance(d, float) else d
 
     s = {"c1": {"v": result["value"], "ms1": r.get("one_batch_in_flight_ms"), "v1": r.get("one_batch_in_flight_images_per_sec"), "dt": "f32",
-                "rf": r["frac"], "mask_rf": r.get("mask_step_frac"), "mask_lit_rf": r.get("mask_step_literal_frac")}}
+                "rf": r.get("frac"), "mask_rf": r.get("mask_step_frac"), "mask_lit_rf": r.get("mask_step_literal_frac")}}
     c = cfg.get("configs[1] f32_split")
     if c:
         s["c1_split"] = {"v": c["value"], "ms1": pick(c, "one_batch_in_flight", "ms_per_step", nd=3), "dt": "f32 via bf16x3", "rf": pick(c, "roofline", "frac", nd=3)}
@@ -1080,6 +1087,29 @@ def write_detail(result, path):
         return None
 
 
+MASK_SAMPLE = 1 << 22          # mask values kept by --dump-outputs (16 MB as float32; the full masks are 8 x 20 x 480 x 640 = 197 MB)
+MASK_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: the arrays a caller of the timed path receives for one batch -- (scores, classes, masks, boxes, query_index)
+    of model.inference -- as <path>/<name>.npy, float32 where the tensor is float32, float64 for the integer ones (exact).  The masks
+    go in as a fixed sample (MASK_SAMPLE flat positions drawn with MASK_SAMPLE_SEED, in increasing order) and as every mask's area
+    (float64), about 16 MB in all.  -> the names written."""
+    import numpy as np
+    scores, classes, masks, boxes, qidx = outputs
+    arrays = {"scores": scores.float(), "classes": classes.double(), "boxes": boxes.float(), "query_index": qidx.double(),
+              "masks_area": masks.sum(dim=(2, 3), dtype=torch.float64)}
+    flat = masks.reshape(-1)
+    idx = np.random.default_rng(MASK_SAMPLE_SEED).choice(flat.numel(), size=min(MASK_SAMPLE, flat.numel()), replace=False)
+    idx.sort()
+    arrays["masks_sample"] = flat[torch.from_numpy(idx).to(flat.device)].float()
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    return sorted(arrays)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def collective_entry(dist, rec, all_gather_s, rccl_log=None):
     """What an N > 1 line says about its only collective: library version, the transport RCCL chose (rank 0's NCCL_DEBUG=INFO
@@ -1088,10 +1118,11 @@ def collective_entry(dist, rec, all_gather_s, rccl_log=None):
     from unseenobjectswithmeanshift_amd.distributed import communicator_report
     el = [r["elapsed_s"] for r in rec]
     out = communicator_report(dist, rccl_log)
-    out.update({"collective": "one all_gather of a per-rank metrics record (5 float64) after the timed region; none on the data path",
-                "all_gather_us": round(1e6 * all_gather_s, 1),
+    out.update({"collective": "one all_gather of a per-rank metrics record (4-5 float64) after the timed region; none on the data path",
                 "per_rank_elapsed_s": {"min": round(min(el), 6), "max": round(max(el), 6), "spread_pct": round(100.0 * (max(el) - min(el)) / max(el), 2),
                                        "slowest_rank": int(max(range(len(el)), key=el.__getitem__))}})
+    if all_gather_s is not None:                    # (timed under --full only)
+        out["all_gather_us"] = round(1e6 * all_gather_s, 1)
     return out
 
 
@@ -1139,15 +1170,20 @@ def stub_main(args, world, rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=120)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="lower bound of the timed region; more steps than --steps are timed if needed")
+    ap.add_argument("--steps", type=int, default=120, help="timed steps (exactly this many)")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed steps before the timed ones")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: one batch in flight, per-kernel timings and rooflines, "
+                         "the 16-bit plans (configs[2]), the mean-shift unit, configs[1..4] sub-results, the CPU baseline")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--full: lower bound of the one-batch timing and of each precision leg")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
     ap.add_argument("--inflight", type=int, default=4,
                     help="batches in flight, one HIP graph + stream each (graphs.PipelinedInference); 1 = one graph on one stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the mean-shift unit and the configs[2..4] sub-results")
-    ap.add_argument("--no-bf16-leg", action="store_true", help="skip the bf16 timing of the per-GPU batch (BASELINE configs[2]) that follows the fp32 region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the mean-shift unit and the configs[2..4] sub-results")
+    ap.add_argument("--no-bf16-leg", action="store_true", help="--full: skip the bf16 timing of the per-GPU batch (BASELINE configs[2]) that follows the fp32 region")
     ap.add_argument("--folded-mask", type=int, default=-1, help="1/0: contract the mask features in factored form (64-channel activation; "
                     "default: the decoder's own default, on) or literally (256-channel mask_features tensor)")
     ap.add_argument("--sparse-taps", action="store_true", help="skip mask rows that feed no attention-mask tap")
@@ -1155,12 +1191,14 @@ def main():
                     help="bf16 (configs 3/5) is NOT the headline configuration: the JSON line then says so in dtype")
     ap.add_argument("--batched-kv", type=int, default=-1, help="1/0: all K/V projections of the decoder in one launch (default: the decoder's own default)")
     ap.add_argument("--no-rccl-report", action="store_true", help="N > 1: do not record rank 0's NCCL_DEBUG=INFO log for the `collective` entry")
-    ap.add_argument("--detail", default=None, help="file that receives the full result document (default gpurun_out/bench_full.json)")
+    ap.add_argument("--detail", default=None, help="--full: file that receives the full result document (default bench_out/bench_full.json)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     # test hooks for the N > 1 code path on a ONE-GPU box (tests/test_gpu_configs.py): every rank on cuda:0, collectives over gloo
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--share-gpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         if not args.stub:
@@ -1199,7 +1237,7 @@ def main():
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.backend == "nccl" and rank == 0 and not args.no_rccl_report and "NCCL_DEBUG" not in os.environ:
+        if args.full and args.backend == "nccl" and rank == 0 and not args.no_rccl_report and "NCCL_DEBUG" not in os.environ:
             # rank 0 records what its communicator runs over (transport per channel, detected topology) into a file of its own --
             # stdout keeps the one JSON line -- and summarises it under `collective` (distributed.parse_rccl_debug)
             rccl_log = f"/tmp/msm_rccl_rank0_{os.getpid()}.log"
@@ -1232,25 +1270,26 @@ def main():
     def step():
         return model.inference(feats, (H, W))
 
+    full = args.full
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
-        out = None
-        for _ in range(max(1, args.warmup) if args.no_graph else 2):
-            out = step()
-        stream.synchronize()
-        graph = None
-        if not args.no_graph:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                out = step()
-        one = graph.replay if graph is not None else step
-        for _ in range(args.warmup):
-            one()
-        stream.synchronize()
         # throughput mode: `inflight` batches in flight, each a HIP graph on its own stream (graphs.PipelinedInference);
         # every slot keeps its own copy of the inputs resident in HBM, a step = one replay of one slot's graph
-        inflight = 1 if graph is None else max(1, args.inflight)
-        pipe = None
+        inflight = 1 if args.no_graph else max(1, args.inflight)
+        out = graph = pipe = None
+        if inflight == 1 or full:
+            # the single-stream form: the timed step itself (inflight 1), or under --full the one-batch figure beside the headline
+            for _ in range(max(1, args.warmup) if args.no_graph else 2):
+                out = step()
+            stream.synchronize()
+            if not args.no_graph:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=stream):
+                    out = step()
+            one = graph.replay if graph is not None else step
+            for _ in range(args.warmup):
+                one()
+            stream.synchronize()
         if inflight > 1:
             from unseenobjectswithmeanshift_amd.graphs import PipelinedInference
             pipe = PipelinedInference(model, depth=inflight)
@@ -1261,69 +1300,71 @@ def main():
                 pipe.submit(None, (H, W), slot_inputs=True)
             pipe.drain()
             one_piped = lambda: pipe.submit(None, (H, W), slot_inputs=True)
-        # step-time estimate -> number of timed steps (>= --steps, >= --min-seconds of work), agreed across the ranks
-        est = timed(one, 10)
-        single_steps = max(args.steps, int(math.ceil(args.min_seconds / max(est, 1e-6))))
         single = None
-        if pipe is not None:
-            single = timed(one, single_steps) * single_steps          # one batch in flight, next to the headline (untimed for `value`)
-            est = timed(one_piped, 4 * inflight)
-        steps = max(args.steps, int(math.ceil(args.min_seconds / max(est, 1e-6))))
-        if dist is not None:
-            t = torch.tensor([steps], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.int64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            steps = int(t.item())
+        if full and pipe is not None:
+            # one batch in flight, next to the headline (untimed for `value`): >= --steps, >= --min-seconds of work
+            est = timed(one, 10)
+            single_steps = max(args.steps, int(math.ceil(args.min_seconds / max(est, 1e-6))))
+            single = timed(one, single_steps) * single_steps
+        steps = args.steps                          # the same on every rank
         run_one = one_piped if pipe is not None else one
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            run_one()
+            last = run_one()
         t_host = time.perf_counter() - t0           # the host's share: Python + hipGraphLaunch per step, the GPU running behind
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        # what one submit costs the host when the queue is NOT full (a full queue makes submit wait for the GPU: t_host above is
-        # then the GPU's time): `inflight` submits into an empty pipeline -- one per slot, none of them waits for its slot's previous
-        # replay --, best of three rounds
-        host_submit_us = float("inf")
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(inflight):
-                run_one()
-            host_submit_us = min(host_submit_us, 1e6 * (time.perf_counter() - t1) / inflight)
-        torch.cuda.synchronize()
-        if pipe is not None:                      # the pipelined slots computed what the single graph computes
-            for a, b in zip(pipe.result(0, wait="host"), out):
-                assert torch.equal(a, b), "pipelined slot differs from the single-stream graph"
-
-        # per-entry-point launch durations of three eager passes: HIP events on this stream around every library launch
-        with _lib.CallTimer() as ct:
+        # what the timed path returned for its last step: the slot's outputs (pipelined), the graph's (one graph) or the pass's (eager)
+        outputs = pipe.result(last, wait="host") if pipe is not None else (out if graph is not None else last)
+        checksum = float(outputs[0].double().sum().item())
+        if args.dump_outputs and rank == 0:
+            names = dump_outputs(outputs, args.dump_outputs)
+            print(f"bench.py: outputs of the last timed step ({', '.join(names)}) written to {args.dump_outputs}", file=sys.stderr, flush=True)
+        if full:
+            # what one submit costs the host when the queue is NOT full (a full queue makes submit wait for the GPU: t_host above is
+            # then the GPU's time): `inflight` submits into an empty pipeline -- one per slot, none of them waits for its slot's previous
+            # replay --, best of three rounds
+            host_submit_us = float("inf")
             for _ in range(3):
-                step()
-            stream.synchronize()
-        dur = ct.durations()
-        mask_graph_ms, mask_calls = mask_step_graph_ms(step, model)
-        # what the default plan runs for the ten predictions: one full-resolution launch, the pooling launch, nine key-resolution launches
-        plan_ms, plan_calls = entry_graph_ms(step, ["mask_logits", "pool_mask_taps", "attn_mask_pooled"])
-        enc_name = {"f32": "encoder_block", "f32_split": "encoder_block_split",
-                    "bf16": "encoder_block_hm" if model.sem_seg_head.pixel_decoder._use_hm() else "encoder_block_lp",
-                    "f16": "encoder_block_hm" if model.sem_seg_head.pixel_decoder._use_hm() else "encoder_block_lp"}[args.precision]
-        enc_ms_all, enc_calls = entry_graph_ms(step, enc_name)
-        launch_label = "eager" if graph is None else ("hipgraph" if pipe is None else
-                                                      f"hipgraph x{inflight}: {inflight} batches of 8 in flight, one graph + stream each")
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(inflight):
+                    run_one()
+                host_submit_us = min(host_submit_us, 1e6 * (time.perf_counter() - t1) / inflight)
+            torch.cuda.synchronize()
+            if pipe is not None:                      # the pipelined slots computed what the single graph computes
+                for a, b in zip(pipe.result(0, wait="host"), out):
+                    assert torch.equal(a, b), "pipelined slot differs from the single-stream graph"
 
-    scores = out[0]
-    checksum = float(scores.double().sum().item())
-    rec = gather_metrics({"images": (hi - lo) * steps, "elapsed_s": elapsed, "checksum": checksum, "pinned": float(affinity["status"] == "pinned"),
-                          "host_submit_us": host_submit_us}, dist, keys=("images", "elapsed_s", "checksum", "pinned", "host_submit_us"))
+            # per-entry-point launch durations of three eager passes: HIP events on this stream around every library launch
+            with _lib.CallTimer() as ct:
+                for _ in range(3):
+                    step()
+                stream.synchronize()
+            dur = ct.durations()
+            mask_graph_ms, mask_calls = mask_step_graph_ms(step, model)
+            # what the default plan runs for the ten predictions: one full-resolution launch, the pooling launch, nine key-resolution launches
+            plan_ms, plan_calls = entry_graph_ms(step, ["mask_logits", "pool_mask_taps", "attn_mask_pooled"])
+            enc_name = {"f32": "encoder_block", "f32_split": "encoder_block_split",
+                        "bf16": "encoder_block_hm" if model.sem_seg_head.pixel_decoder._use_hm() else "encoder_block_lp",
+                        "f16": "encoder_block_hm" if model.sem_seg_head.pixel_decoder._use_hm() else "encoder_block_lp"}[args.precision]
+            enc_ms_all, enc_calls = entry_graph_ms(step, enc_name)
+        launch_label = "eager" if graph is None and pipe is None else ("hipgraph" if pipe is None else
+                                                                       f"hipgraph x{inflight}: {inflight} batches of 8 in flight, one graph + stream each")
+
+    mine = {"images": (hi - lo) * steps, "elapsed_s": elapsed, "checksum": checksum, "pinned": float(affinity["status"] == "pinned")}
+    if full:
+        mine["host_submit_us"] = host_submit_us
+    rec = gather_metrics(mine, dist, keys=tuple(mine))
     # BASELINE configs[2] is a bf16 configuration (batch 64 over 8 GPUs): every rank also times its batch of 8 in the low-precision
     # mode, same barriers, same max-over-ranks rule -- a `configs` entry of the line, never `value`
     lp_rec = None
-    if args.precision == "f32" and not args.no_graph and not args.no_bf16_leg:
+    if full and args.precision == "f32" and not args.no_graph and not args.no_bf16_leg:
         del pipe, graph
         pipe = graph = None
         with torch.cuda.stream(stream):
@@ -1331,7 +1372,7 @@ def main():
             h_images, h_elapsed, h_steps, h_single, h_roof = precision_leg(model, feats, dev, dist, args, "f16", max(1, args.inflight))
         lp_rec = gather_metrics({"images": lp_images, "elapsed_s": lp_elapsed, "single_s": lp_single}, dist, keys=("images", "elapsed_s", "single_s"))
         h_rec = gather_metrics({"images": h_images, "elapsed_s": h_elapsed, "single_s": h_single}, dist, keys=("images", "elapsed_s", "single_s"))
-    ag_s = timed_all_gather(dist)                   # every rank takes part: the path's only collective, timed on its own
+    ag_s = timed_all_gather(dist) if full else None     # every rank takes part: the path's only collective, timed on its own
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -1340,6 +1381,43 @@ def main():
     total_images = sum(r["images"] for r in rec)
     collective = collective_entry(dist, rec, ag_s, rccl_log)
     bf16 = args.precision in ("bf16", "f16")
+    result = {
+        "metric": METRIC,
+        "value": round(total_images / t_max, 2),
+        "unit": "images/sec",
+        "n_gpus": world,
+        "steps": steps,
+        "steps_requested": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * t_max / steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if not bf16 else f"{args.precision} operands / fp32 accumulation (NOT the headline configuration)",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]: batch 8 of 640x480 per GPU, ResNet-50 features -> MSDeformAttn pixel decoder -> 9-layer decoder, 100 q -> top-20",
+                   "workload_detail": "configs[1]: batch=8 640x480 frames per GPU, synthetic ResNet-50 res2..res5 features "
+                                      "-> MSDeformAttn pixel decoder (6 layers) -> 9-layer hypersphere decoder (100 queries) "
+                                      "-> top-20 instance post-processing; backbone excluded",
+                   "global_batch": world * BATCH, "per_gpu_batch": BATCH, "launch": launch_label,
+                   "batches_in_flight": inflight,
+                   "sparse_taps": bool(args.sparse_taps), "folded_mask_step": bool(pred.folded_mask_features),
+                   "configs2_plan": "f16 (IEEE-half operands, fp32 accumulation); the bf16 plan is reported beside it as c2_bf16",
+                   "parallelism": f"dp{world}"},
+        "per_rank": [{"rank": i, "images_per_sec": round(r["images"] / r["elapsed_s"], 2), "checksum": r["checksum"],
+                      "numa_pinned": bool(r["pinned"])} for i, r in enumerate(rec)],
+        "roofline": {},
+    }
+    result["config"]["rank0_cpu_affinity"] = affinity
+    result["config"]["GPU_MAX_HW_QUEUES"] = os.environ.get("GPU_MAX_HW_QUEUES")
+    result["config"]["visible_gpus"] = have
+    if not full:
+        # a plain run: the headline and nothing else (the rest is --full's)
+        result["collective"] = collective if world > 1 else {"world_size": 1}
+        print(json.dumps(compact_line(result)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     mask_name = "msm_mask_logits_bf16_fwd" if (bf16 and "msm_mask_logits_bf16_fwd" in dur) else "msm_mask_logits_fwd"
     per_call = dur[mask_name]
     calls_per_step = mask_calls
@@ -1417,46 +1495,20 @@ def main():
     roofline["mask_step_literal_frac"] = None           # filled from configs["configs[1] literal mask step"] below (N = 1 with extras)
     kernels = {k: {"launches_per_step": len(v) // 3, "ms_per_step": round(sum(v) / 3, 4), "avg_launch_us": round(1e3 * sum(v) / len(v), 2)}
                for k, v in sorted(dur.items(), key=lambda kv: -sum(kv[1]))}
-    result = {
-        "metric": METRIC,
-        "value": round(total_images / t_max, 2),
-        "unit": "images/sec",
-        "n_gpus": world,
-        "steps": steps,
-        "steps_requested": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * t_max / steps, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if not bf16 else f"{args.precision} operands / fp32 accumulation (NOT the headline configuration)",
-        "data": "synthetic",
-        "config": {"workload": "configs[1]: batch 8 of 640x480 per GPU, ResNet-50 features -> MSDeformAttn pixel decoder -> 9-layer decoder, 100 q -> top-20",
-                   "workload_detail": "configs[1]: batch=8 640x480 frames per GPU, synthetic ResNet-50 res2..res5 features "
-                                      "-> MSDeformAttn pixel decoder (6 layers) -> 9-layer hypersphere decoder (100 queries) "
-                                      "-> top-20 instance post-processing; backbone excluded",
-                   "global_batch": world * BATCH, "per_gpu_batch": BATCH, "launch": launch_label,
-                   "batches_in_flight": inflight,
-                   "sparse_taps": bool(args.sparse_taps), "folded_mask_step": folded, "attention_masks_at_key_resolution": pooled_plan,
-                   "configs2_plan": "f16 (IEEE-half operands, fp32 accumulation); the bf16 plan is reported beside it as c2_bf16",
-                   "parallelism": f"dp{world}"},
-        "per_rank": [{"rank": i, "images_per_sec": round(r["images"] / r["elapsed_s"], 2), "checksum": r["checksum"],
-                      "numa_pinned": bool(r["pinned"]), "host_submit_us_per_step": round(r["host_submit_us"], 1)} for i, r in enumerate(rec)],
-        "roofline": roofline,
-        "kernels": {"launch": "eager, HIP events on the launch stream around every library entry point, mean of 3 passes", "by_entry_point": kernels,
-                    "sum_ms_per_step": round(sum(v["ms_per_step"] for v in kernels.values()), 4)},
-    }
+    result["config"]["attention_masks_at_key_resolution"] = pooled_plan
+    for p, r in zip(result["per_rank"], rec):
+        p["host_submit_us_per_step"] = round(r["host_submit_us"], 1)
+    result["roofline"] = roofline
+    result["kernels"] = {"launch": "eager, HIP events on the launch stream around every library entry point, mean of 3 passes", "by_entry_point": kernels,
+                         "sum_ms_per_step": round(sum(v["ms_per_step"] for v in kernels.values()), 4)}
     if single is not None:
         # rank 0's own clock, one batch in flight (one graph, one stream): the latency-oriented figure
         result["one_batch_in_flight"] = {"value": round((hi - lo) * single_steps / single, 2), "unit": "images/sec",
                                          "ms_per_step": round(1e3 * single / single_steps, 4), "steps": single_steps}
-    result["config"]["rank0_cpu_affinity"] = affinity
     # multi-GPU readiness (no 8-GPU node was available to the builder): what a rank's host spends per step, and the hardware-queue
     # budget the streams of the pipelined mode share
     result["host_submit_us_per_step"] = round(host_submit_us, 1)
     result["host_loop_share_of_step"] = round(t_host / elapsed, 3)
-    result["config"]["GPU_MAX_HW_QUEUES"] = os.environ.get("GPU_MAX_HW_QUEUES")
-    result["config"]["visible_gpus"] = have
     if lp_rec is not None:
         lp_t = max(r["elapsed_s"] for r in lp_rec)
         result.setdefault("configs", {})["configs[2] bf16"] = {
@@ -1498,7 +1550,7 @@ def main():
     result["summary"] = build_summary(result)
     # stdout carries ONE compact line (<= LINE_BUDGET bytes: the driver's record holds the last 8 KB of stdout); the full document --
     # `kernels`, `configs`, `mean_shift`, per-rank detail -- goes to a file (copied to profiles/ from the builder's runs)
-    detail = write_detail(result, args.detail or os.path.join(ROOT, "gpurun_out", "bench_full.json"))
+    detail = write_detail(result, args.detail or os.path.join(ROOT, "bench_out", "bench_full.json"))
     print(f"bench.py: full result ({len(json.dumps(result))} bytes) written to {detail}", file=sys.stderr, flush=True)
     print(json.dumps(compact_line(result, detail and os.path.relpath(detail, ROOT))), flush=True)
     if dist is not None:

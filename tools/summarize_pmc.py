@@ -20,7 +20,7 @@ kernels = sorted(vals["MfmaUtil"], key=lambda k: -sum(vals["MfmaUtil"][k]))
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 with open(os.path.join(root, "profiles", f"{rnd}_pmc_mfma_lds.md"), "w") as out:
     out.write(f"# rocprofv3 --pmc MfmaUtil / LDSBankConflict / LdsUtil ({rnd}), per-dispatch averages (%)\n")
-    out.write("command (one pass per counter): `rocprofv3 --pmc <counter> --output-format csv -- python bench.py --steps 2 --warmup 1 "
+    out.write("command (one pass per counter): `rocprofv3 --pmc <counter> --output-format csv -- python bench.py --full --steps 2 --warmup 1 "
               "--no-graph --no-cpu-baseline` (tools/profile_round.sh)\n")
     out.write("MfmaUtil = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE * SIMDs); LDSBankConflict = share of GPU time the LDS is stalled by "
               "bank conflicts; LdsUtil = SQ_LDS_IDX_ACTIVE / (GRBM_GUI_ACTIVE * CUs).  Rows ordered by total MFMA-busy time.\n\n")

@@ -17,7 +17,7 @@ rows = list(csv.DictReader(open(stats)))
 with open(f"profiles/{tag}_kernel_stats.md", "w") as f:
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     f.write(f"# rocprofv3 --kernel-trace --stats summary ({tag})\n\n")
-    f.write("command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 10 --warmup 2 --no-graph --no-cpu-baseline "
+    f.write("command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-graph --no-cpu-baseline "
             "--no-extras --min-seconds 0` (tools/profile_round.sh; 25-30 passes of the hot path per run: warm-up, step estimate, timed, "
             "event-timed -- plus the roofline legs of bench.py: 100 extra encoder-block replays and the full-resolution mask-step "
             "launches, which is why those kernels have more calls than 6 / 1 per pass)\n\n")
