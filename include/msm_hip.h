@@ -41,6 +41,8 @@
  *   msm_label_stats              <- per-label loops of the two-stage harness, lib/fcn/test_dataset.py:62-131,183-198
  *   msm_label_image / msm_crop_resize / msm_paste_labels
  *                                <- combine_masks test_utils.py:93-112, crop_rois test_dataset.py:62-112, paste-back :160-177, batched
+ *   msm_eval_counts              <- the per-label-pair loops of multilabel_metrics, lib/utils/evaluation.py:109-258
+ *                                   (seg2bmap :15-69, boundary_overlap :71-104)
  *   msm_instance_postprocess     <- F.interpolate + instance_inference,
  *                                   MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:337-343,461-497
  */
@@ -59,7 +61,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 22   /* 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 23   /* 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -903,6 +905,33 @@ int msm_crop_resize(const float* rgb, const float* depth, const float* labels, c
                     float* depth_out, float* mask_out, int N, int H, int W, int S, void* stream);
 int msm_paste_labels(const float* renum, const int32_t* table, const int32_t* order, const int32_t* frame_start,
                      float* refined, int F, int H, int W, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Segmentation metrics: every integer count of multilabel_metrics (lib/utils/evaluation.py:109-258) for B pairs of label
+ * images in one pass each, instead of the reference's per-(gt label, predicted label) masks, seg2bmap boundary maps
+ * (:15-69) and disk dilations (boundary_overlap, :71-104).
+ *   pred, gt  [B][H][W] float, integer valued in [0, 1024) (LABEL_BINS); other values are counted in the header
+ *   radius    disk radius of the boundary dilation, 0..16 (the reference: ceil(0.003 * sqrt(H^2 + W^2)))
+ *   L         capacity of the per-side label tables (1..1024; L <= 64 is one pass, more labels one pass per pair of
+ *             64-label chunks)
+ *   counts    [B][8 + 6L + 3L^2] int32, per image:
+ *               [0] n_gt, [1] n_pred      non-zero labels present (may exceed L: then only the first L are tabled,
+ *                                         callers rerun with a larger L)
+ *               [2] / [3]                 gt / pred pixels that are not integers in [0, 1024) (callers raise)
+ *               [4] / [5]                 gt / pred pixels with a non-zero label
+ *               [6], [7]                  0
+ *             then, over the dense indices (labels in ascending order, background excluded):
+ *               lab_gt[L], lab_pred[L]    label value of each index
+ *               area_gt[L], area_pred[L]  pixels per label
+ *               bnd_gt[L], bnd_pred[L]    pixels of seg2bmap(gt == label), seg2bmap(pred == label)
+ *               tp[L][L]                  [i][j] pixels with gt label i and predicted label j
+ *               fgm[L][L]                 [i][j] boundary pixels of pred label j within disk(radius) of a boundary pixel of gt label i
+ *               gtm[L][L]                 [i][j] boundary pixels of gt label i within disk(radius) of a boundary pixel of pred label j
+ *   workspace msm_eval_counts_workspace(B) bytes (device)
+ * Every count is exact. */
+int64_t msm_eval_counts_workspace(int B);
+int msm_eval_counts(const float* pred, const float* gt, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                    int B, int H, int W, int radius, int L, void* stream);
 
 #ifdef __cplusplus
 }

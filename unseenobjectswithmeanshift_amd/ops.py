@@ -1333,6 +1333,28 @@ def label_stats(labels, weight=None, k=1024):
     return stats, wsum, overflow
 
 
+
+def eval_counts_row(L):
+    """int32 values per image of msm_eval_counts' counts table at label capacity L."""
+    return 8 + 6 * int(L) + 3 * int(L) * int(L)
+
+
+def eval_counts(pred, gt, radius, L=64):
+    """Integer counts of multilabel_metrics for B pairs of label images (msm_eval_counts): pred, gt (B,H,W) float32 with
+    integer values in [0, 1024), disk radius `radius` -> counts (B, eval_counts_row(L)) int32 laid out as include/msm_hip.h
+    documents (header, label tables, tp / fgm / gtm [L][L])."""
+    _c(pred, "pred"), _c(gt, "gt")
+    if pred.shape != gt.shape or pred.dim() != 3:
+        raise RuntimeError(f"eval_counts: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be the same (B,H,W)")
+    B, H, W = pred.shape
+    dev = pred.device
+    counts = torch.empty((B, eval_counts_row(L)), device=dev, dtype=torch.int32)
+    nbytes = lib().msm_eval_counts_workspace(B)
+    ws = torch.empty((max(1, nbytes // 4),), device=dev, dtype=torch.int32)
+    check(lib().msm_eval_counts(_p(pred), _p(gt), _p(counts), _p(ws), nbytes, B, H, W, int(radius), int(L), _stream()),
+          "msm_eval_counts")
+    return counts
+
 def label_image(masks, inst_labels):
     """masks (B,K,H,W) float (non-zero = inside), inst_labels (B,K) float -> (B,H,W) float label images (msm_label_image)."""
     _c(masks, "masks"), _c(inst_labels, "inst_labels")

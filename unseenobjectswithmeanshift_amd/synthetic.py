@@ -302,3 +302,77 @@ class StandInBackbone(torch.nn.Module):
             b, c, h, ww = p.shape
             out[name] = torch.bmm(w.unsqueeze(0).expand(b, -1, -1), p.reshape(b, c, h * ww)).relu_().view(b, -1, h, ww)
         return out
+
+
+def _plant(img, rng, n, values, H, W, near=None):
+    """Plant n shapes (rectangles and ellipses in turn; later ones overwrite earlier ones) with the given label values.
+    near: optional list of (cy, cx, ry, rx) the k-th shape jitters around."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    shapes = []
+    for k in range(n):
+        if near is not None and k < len(near):
+            cy, cx, ry, rx = near[k]
+            cy, cx = cy + rng.integers(-4, 5), cx + rng.integers(-4, 5)
+            ry, rx = max(2, int(ry * rng.uniform(0.8, 1.2))), max(2, int(rx * rng.uniform(0.8, 1.2)))
+        else:
+            cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+            ry, rx = int(rng.integers(max(2, H // 20), max(3, H // 6))), int(rng.integers(max(2, W // 20), max(3, W // 6)))
+        shapes.append((cy, cx, ry, rx))
+        if k % 2 == 0:
+            m = (np.abs(yy - cy) <= ry) & (np.abs(xx - cx) <= rx)
+        else:
+            m = ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0
+        img[m] = values[k]
+    return shapes
+
+
+def synth_label_pair(H, W, seed, kind="blobs", n_gt=8, n_pred=8, gt_values=None, pred_values=None):
+    """Seeded (prediction, gt) pair of (H,W) float32 label images (0 = background) for the segmentation-metric tests.
+    kind: "blobs" (prediction shapes jitter around the gt shapes, extra ones elsewhere, labels in another order), "edges"
+    (objects on the last row, the last column and the corner), "full_gt" / "full_both" (a label covering the whole image),
+    "empty_pred" / "empty_gt" / "empty_both", "ties" (two mirrored gt objects one predicted object covers equally), "grid" (gt
+    a grid of n_gt small rectangles)."""
+    rng = np.random.default_rng(seed)
+    gv = list(gt_values) if gt_values is not None else list(range(1, n_gt + 1))
+    pv = list(pred_values) if pred_values is not None else [int(v) for v in rng.permutation(np.arange(1, n_pred + 1))]
+    gt = np.zeros((H, W), np.float32)
+    pred = np.zeros((H, W), np.float32)
+    if kind in ("blobs", "edges", "full_gt", "empty_pred", "empty_gt"):
+        shapes = _plant(gt, rng, len(gv), gv, H, W)
+        _plant(pred, rng, len(pv), pv, H, W, near=shapes)
+        if kind == "edges":
+            gt[H - 5:, W // 3: W // 2] = gv[0]
+            gt[H // 4: H // 2, W - 3:] = gv[-1]
+            gt[H - 7:, W - 9:] = gv[1 % len(gv)]
+            pred[H - 3:, W // 3 - 4: W // 2 - 2] = pv[0]
+            pred[H // 4 + 2: H // 2 + 3, W - 6:] = pv[-1]
+            pred[H - 1:, W - 1:] = pv[1 % len(pv)]
+            pred[0, :] = pv[0]
+        if kind == "full_gt":
+            gt[:] = gv[0]
+        if kind == "empty_pred":
+            pred[:] = 0
+        if kind == "empty_gt":
+            gt[:] = 0
+    elif kind == "empty_both":
+        pass
+    elif kind == "full_both":
+        gt[:] = gv[0]
+        pred[:] = pv[0]
+    elif kind == "ties":
+        h, w = H // 4, W // 6
+        y0 = H // 2 - h // 2
+        gt[y0:y0 + h, W // 2 - 2 * w: W // 2 - w] = gv[0]
+        gt[y0:y0 + h, W // 2 + w: W // 2 + 2 * w] = gv[1]
+        pred[y0 + 2:y0 + h - 2, W // 2 - 2 * w + w // 2: W // 2 + 2 * w - w // 2] = pv[0]
+        pred[2:2 + h // 2, 2:2 + w] = pv[1 % len(pv)]
+    elif kind == "grid":
+        k = int(np.ceil(np.sqrt(len(gv))))
+        ch, cw = H // k, W // k
+        for n, v in enumerate(gv):
+            r, c = divmod(n, k)
+            gt[r * ch + 1: r * ch + ch - 1, c * cw + 1: c * cw + cw - 1] = v
+        _plant(pred, rng, len(pv), pv, H, W)
+    else:
+        raise ValueError(kind)
+    return pred, gt

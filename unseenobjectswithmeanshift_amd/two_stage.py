@@ -9,6 +9,10 @@ return values:
   nms                       <- lib/fcn/nms.py:3-23
   combine_masks_with_NMS    <- lib/fcn/test_utils.py:55-91
   test_sample_crop_nolabel  <- lib/fcn/test_utils.py:339-421
+  test_sample               <- lib/fcn/test_utils.py:169-205   (labelled: scored with evaluation.multilabel_metrics)
+  test_sample_crop          <- lib/fcn/test_utils.py:245-336
+  test_dataset(_crop)       <- lib/fcn/test_utils.py:424-513   (the printed means, returned)
+  test_batch_crop           the labelled form of test_batch_crop_nolabel (one metrics call per batch)
 
 These are data-dependent, tiny (<= 20 instances) bookkeeping steps; they run as torch ops on
 whatever device the label maps live on (GPU in production, CPU in the unit tests), never through
@@ -16,7 +20,11 @@ the oracle.  Differences from the reference, on purpose:
   * the second stage is BATCHED: all crops of an image go through the crop predictor in one call
     (the reference loops batch-1, test_utils.py:396-405);
   * test_sample_crop_nolabel returns (out_label, out_label_refined, out_score, bbox) with None for
-    the last two when NMS is off -- the reference raises NameError there (test_utils.py:376,421).
+    the last two when NMS is off -- the reference raises NameError there (test_utils.py:376,421);
+  * test_sample / test_sample_crop read the ground truth from sample["label"], else sample["labels"] -- the reference's
+    test_sample_crop tests "label" twice (test_utils.py:252-255), so a sample with "labels" only has no ground truth there
+    and multilabel_metrics fails on it;
+  * the labelled functions return the metrics (and test_dataset / test_dataset_crop the means) instead of printing them.
 """
 import numpy as np
 import torch
@@ -245,6 +253,13 @@ def test_sample_crop_nolabel(sample, predictor, predictor_crop=None, *, use_dept
     sample: {"image_color" (3,H,W), "depth" (3,H,W) xyz (when use_depth), ...}.  `predictor(sample)`
     returns {"instances": Instances}; `predictor_crop` is called ONCE with a list of crop samples
     (batched) when it exposes ``batch_call``, else once per crop."""
+    return _sample_crop(sample, predictor, predictor_crop, use_depth=use_depth, topk=topk, confident_score=confident_score,
+                        low_threshold=low_threshold, num_class=num_class, use_nms=use_nms, depth_threshold=depth_threshold)[1:]
+
+
+def _sample_crop(sample, predictor, predictor_crop, *, use_depth, topk, confident_score, low_threshold, num_class, use_nms,
+                 depth_threshold):
+    """test_sample_crop_nolabel's steps -> (first-stage label image before the depth filter, out_label, refined, out_score, bbox)."""
     image = sample["image_color"]
     if image.dim() == 4:
         image = image[0]
@@ -277,7 +292,68 @@ def test_sample_crop_nolabel(sample, predictor, predictor_crop=None, *, use_dept
                 lab, _, _ = _labels_from_outputs(o, topk, confident_score, low_threshold, num_class, use_nms)
                 labels_crop[i] = torch.as_tensor(lab).to(dev)
             refined, _ = match_label_crop(out_label, labels_crop, out_label_crop, rois, depth_crop)
-    return out_label, refined, out_score, bbox
+    return label, out_label, refined, out_score, bbox
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The labelled harness (lib/fcn/test_utils.py:169-205, 245-336, 424-513): the same pipelines, scored against the sample's
+# ground truth with evaluation.multilabel_metrics.
+# ----------------------------------------------------------------------------------------------------------------------
+def _sample_gt(sample):
+    """The ground-truth label image of a sample: sample["label"], else sample["labels"], squeezed to (H,W)."""
+    gt = sample["label"] if "label" in sample else sample["labels"]
+    gt = torch.as_tensor(gt)
+    return gt.reshape(gt.shape[-2:])
+
+
+def test_sample(sample, predictor, *, topk=False, confident_score=0.9, low_threshold=0.4, num_class=2, use_nms=False):
+    """lib/fcn/test_utils.py:169-205: the first-stage label image of sample["image_color"] scored against the sample's ground
+    truth -> the multilabel_metrics dict."""
+    from .evaluation import multilabel_metrics
+    image = sample["image_color"]
+    if image.dim() == 4:
+        image = image[0]
+    sample = dict(sample, image=image, height=image.shape[-2], width=image.shape[-1])
+    sample.setdefault("depth", None)
+    label, _, _ = _labels_from_outputs(predictor(sample), topk, confident_score, low_threshold, num_class, use_nms)
+    return multilabel_metrics(torch.as_tensor(label).to(image.device), _sample_gt(sample))
+
+
+def test_sample_crop(sample, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4,
+                     num_class=2, use_nms=False, depth_threshold=0.5):
+    """lib/fcn/test_utils.py:245-336: test_sample_crop_nolabel's pipeline scored against the sample's ground truth ->
+    (metrics, metrics_refined).  As in the reference:
+      * ``metrics`` scores the combined first-stage label image BEFORE the depth filter;
+      * ``metrics_refined`` scores the refined label image, or -- no second stage, or no crop -- the depth-filtered
+        first-stage image;
+      * the ground truth is sample["label"], else sample["labels"] (the reference tests "label" twice and never reads
+        "labels", so a sample with "labels" only is scored against None there, test_utils.py:252-255)."""
+    from .evaluation import multilabel_metrics
+    gt = _sample_gt(sample)
+    label, out_label, refined, _, _ = _sample_crop(sample, predictor, predictor_crop, use_depth=use_depth, topk=topk,
+                                                   confident_score=confident_score, low_threshold=low_threshold,
+                                                   num_class=num_class, use_nms=use_nms, depth_threshold=depth_threshold)
+    dev = out_label.device
+    metrics = multilabel_metrics(torch.as_tensor(label).to(dev), gt)
+    metrics_refined = multilabel_metrics((refined if refined is not None else out_label)[0], gt)
+    return metrics, metrics_refined
+
+
+def test_dataset(dataset, predictor, **kw):
+    """lib/fcn/test_utils.py:424-460: test_sample over every sample of ``dataset`` -> the per-key mean (evaluation.average_metrics).
+    Keyword arguments as test_sample (the reference's defaults here: topk=False, confident_score=0.7)."""
+    from .evaluation import average_metrics
+    kw = dict(dict(topk=False, confident_score=0.7, low_threshold=0.4), **kw)
+    return average_metrics([test_sample(dataset[i], predictor, **kw) for i in range(len(dataset))])
+
+
+def test_dataset_crop(dataset, predictor, predictor_crop, **kw):
+    """lib/fcn/test_utils.py:462-513: test_sample_crop over every sample -> (mean metrics, mean refined metrics).  Keyword
+    arguments as test_sample_crop (the reference's defaults here: topk=True, confident_score=0.9)."""
+    from .evaluation import average_metrics
+    kw = dict(dict(topk=True, confident_score=0.9, low_threshold=0.4), **kw)
+    pairs = [test_sample_crop(dataset[i], predictor, predictor_crop, **kw) for i in range(len(dataset))]
+    return average_metrics([p[0] for p in pairs]), average_metrics([p[1] for p in pairs])
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -438,6 +514,14 @@ def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_dept
     None, rows) -- frame f's results equal test_sample_crop_nolabel(samples[f], ...)[0][0] / [1][0]; ``rows`` is the ROI table
     (frame, label, x0, y0, x1, y1, 0, 0) of the second stage.  ``stages``: a dict that receives the intermediate tensors
     (crops, second-stage label images) -- for tests."""
+    return _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk, confident_score=confident_score,
+                       low_threshold=low_threshold, num_class=num_class, depth_threshold=depth_threshold, crop_batch=crop_batch,
+                       stages=stages)[1:]
+
+
+def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confident_score, low_threshold, num_class, depth_threshold,
+                crop_batch, stages):
+    """test_batch_crop_nolabel's steps -> (first-stage label images before the depth filter, out_label, refined, rows)."""
     images = torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples]).float().contiguous()
     Fr, _, H, W = images.shape
     depths = None
@@ -446,19 +530,19 @@ def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_dept
     first = [{"image": images[f], "depth": depths[f] if depths is not None else None, "height": H, "width": W} for f in range(Fr)]
     kw = dict(topk=topk, confident_score=confident_score, low_threshold=low_threshold, num_class=num_class)
     scores, classes, masks = _batch_tensors(predictor, first)
-    out_label = _label_image_batched(masks, instance_labels(scores, classes, **kw))
+    label = out_label = _label_image_batched(masks, instance_labels(scores, classes, **kw))
     if depths is not None:
         thr = torch.tensor([0.8 if "OSD" in str(s.get("file_name", "")) else depth_threshold for s in samples],
                            device=images.device, dtype=torch.float32)[:, None]          # test_utils.py:384-387
         out_label = filter_labels_depth(out_label, depths, thr)
     if predictor_crop is None:
-        return out_label, None, []
+        return label, out_label, None, []
     stats, _, overflow = label_stats(out_label)
     packed = torch.cat([stats.reshape(-1), overflow]).cpu().numpy()                      # the batch's first transfer
     rows = roi_table(packed[:-Fr].reshape(Fr, -1, 5), packed[-Fr:], H, W)
     n = len(rows)
     if n == 0:
-        return out_label, torch.zeros_like(out_label), rows
+        return label, out_label, torch.zeros_like(out_label), rows
     rgb_crop, mask_crop, depth_crop = _crop_resize_batched(images, depths, out_label, rows, CROP_SIZE)
     labels_crop = torch.empty((n, CROP_SIZE, CROP_SIZE), device=images.device, dtype=torch.float32)
     for c0 in range(0, n, crop_batch):
@@ -470,7 +554,29 @@ def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_dept
     if stages is not None:
         stages.update(rgb_crop=rgb_crop, mask_crop=mask_crop, depth_crop=depth_crop, labels_crop=labels_crop.clone())
     refined = match_label_crop_batched(out_label, labels_crop, mask_crop, rows, depth_crop)
-    return out_label, refined, rows
+    return label, out_label, refined, rows
+
+
+def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4,
+                    num_class=2, depth_threshold=0.5, crop_batch=256):
+    """The labelled form of test_batch_crop_nolabel: every frame of the batch scored against its sample's ground truth
+    ("label", else "labels") -> (metrics, metrics_refined), two lists of per-frame dicts equal to test_sample_crop(samples[f],
+    ...): the first-stage label image before the depth filter, and the refined image of a frame that has crops, else its
+    depth-filtered first-stage image.  All 2F images are scored by ONE evaluation.multilabel_metrics_batched call."""
+    from .evaluation import multilabel_metrics_batched
+    label, out_label, refined, rows = _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk,
+                                                  confident_score=confident_score, low_threshold=low_threshold, num_class=num_class,
+                                                  depth_threshold=depth_threshold, crop_batch=crop_batch, stages=None)
+    Fr = label.shape[0]
+    dev = label.device
+    gt = torch.stack([_sample_gt(s).to(dev).float() for s in samples])
+    second = out_label.float()
+    if refined is not None:
+        cropped = torch.zeros(Fr, dtype=torch.bool)
+        cropped[sorted({r[0] for r in rows})] = True
+        second = torch.where(cropped.to(dev)[:, None, None], refined.float(), second)
+    m = multilabel_metrics_batched(torch.cat([label.float(), second]), torch.cat([gt, gt]))
+    return m[:Fr], m[Fr:]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
