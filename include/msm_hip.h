@@ -61,7 +61,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 23   /* 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 24   /* 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -932,6 +932,59 @@ int msm_paste_labels(const float* renum, const int32_t* table, const int32_t* or
 int64_t msm_eval_counts_workspace(int B);
 int msm_eval_counts(const float* pred, const float* gt, int32_t* counts, void* workspace, int64_t workspace_bytes,
                     int B, int H, int W, int radius, int L, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Set criterion (MSMFormer/meanshiftformer/modeling/matcher.py, criterion.py): Hungarian matching costs and the point-sampled
+ * sigmoid-CE / dice mask losses of every prediction of one criterion call (final + auxiliary), a few launches in all.
+ * point_sample(x, c) = grid_sample(x, 2c - 1, bilinear, zeros padding, align_corners=False); c[..., 0] is x (width).
+ * Shared arguments:
+ *   n_pred       predictions (the final one and the auxiliary ones), all (B, Q, C1) logits and (B, Q, Hm, Wm) masks, fp32
+ *   tgt          [TT][Hg][Wg] uint8 (0 / 1) target masks of the batch, image b's at rows toff[b] .. toff[b + 1]
+ *
+ * msm_match_cost: the matcher's cost matrices (matcher.py:15-64, 98-149) for every (prediction, image), one launch.
+ *   table        device int64 [2 n_pred + B + 1]: pred_logits base pointers, pred_masks base pointers, then toff[0..B]
+ *   labels       [TT] int32 class of every target (in [0, C1); others give a nan cost)
+ *   points       [n_pred][B][P][2] the matcher's random points (one torch.rand(1, P, 2) per prediction and image)
+ *   cost         [n_pred][Q][TT] fp32: image b's matrix is columns toff[b] .. toff[b + 1]; other entries are not written
+ *                C = w_mask (sum_p softplus(x) - x y) / P - w_class softmax(logits_q)[label_t]
+ *                    + w_dice (1 - (2 sum_p sigmoid(x) y + 1) / (sum_p sigmoid(x) + sum_p y + 1))
+ *   max_T        max_b (toff[b + 1] - toff[b])
+ *
+ * msm_point_loss_fwd: SetCriterion.loss_masks (criterion.py:140-190) with detectron2's
+ * get_uncertain_point_coords_with_randomness for every matched (prediction, mask): the k = int(importance_ratio P) points of
+ * largest uncertainty -|x| among the Pos oversampled ones (an exact top-k set, ties to the lower index), then the P - k
+ * uniform points; x and y sampled at those P points.
+ *   table        device int64 [n_pred]: pred_masks base pointers
+ *   pairs        [n_pred N][4] int32: prediction, row n < N of its random points, b Q + q, target row in tgt; the N pairs of
+ *                a prediction are in the reference's order (images in order, queries ascending)
+ *   os_points    [n_pred][N][Pos][2] the oversampled points, rnd_points [n_pred][N][P - k][2] the uniform ones
+ *   losses       [2][n_pred] fp32: loss_mask = sum_n (sum_p BCE(x_p, y_p) / P) / num_masks, loss_dice = sum_n (1 - (2a + 1) /
+ *                (b + 1)) / num_masks with a = sum sigmoid(x) y, b = sum sigmoid(x) + sum y; the per-mask terms are summed in a
+ *                fixed order, so the values repeat bit for bit.  N = 0: zeros.
+ *   sel_bits     [n_pred N][ceil(Pos / 32)] uint32: bit i % 32 of word i / 32 set when oversampled point i is selected
+ *   workspace    msm_point_loss_workspace(n_pred N, k) bytes (device), read by the backward: per pair the float4 (BCE mean,
+ *                dice, a, b), then per pair the k selected indices in ascending order
+ *
+ * msm_point_loss_bwd: grad_losses [2][n_pred] (d/d loss_mask, d/d loss_dice) -> the gradient of every matched mask, scattered
+ * through the four bilinear weights of every point (sigma and y recomputed at the saved points).
+ *   table        device int64 [2 n_pred]: pred_masks base pointers, then the gradient base pointers ([B][Q][Hm][Wm] each,
+ *                zero-initialised by the caller; only matched masks are written)
+ *   flags        MSM_POINT_LOSS_GLOBAL_ATOMICS: scatter with global float atomics even where the mask fits in LDS
+ *                (Hm Wm 4 <= 128 KiB: one workgroup accumulates its mask in LDS and writes it out whole).  The float atomics
+ *                make the gradient's last bits depend on arrival order. */
+#define MSM_POINT_LOSS_GLOBAL_ATOMICS 1
+int msm_match_cost(const int64_t* table, const uint8_t* tgt, const int32_t* labels, const float* points, float* cost,
+                   int n_pred, int B, int Q, int C1, int Hm, int Wm, int Hg, int Wg, int P, int TT, int max_T,
+                   float w_class, float w_mask, float w_dice, void* stream);
+int64_t msm_point_loss_workspace(int n_pairs, int k);
+int msm_point_loss_fwd(const int64_t* table, const uint8_t* tgt, const int32_t* pairs, const float* os_points,
+                       const float* rnd_points, float* losses, uint32_t* sel_bits, void* workspace, int64_t workspace_bytes,
+                       int n_pred, int N, int BQ, int TT, int Hm, int Wm, int Hg, int Wg, int Pos, int k, int P,
+                       float num_masks, void* stream);
+int msm_point_loss_bwd(const int64_t* table, const uint8_t* tgt, const int32_t* pairs, const float* os_points,
+                       const float* rnd_points, const void* workspace, int64_t workspace_bytes, const float* grad_losses,
+                       int n_pred, int N, int BQ, int TT, int Hm, int Wm, int Hg, int Wg, int Pos, int k, int P,
+                       float num_masks, int flags, void* stream);
 
 #ifdef __cplusplus
 }

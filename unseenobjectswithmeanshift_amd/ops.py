@@ -1355,6 +1355,120 @@ def eval_counts(pred, gt, radius, L=64):
           "msm_eval_counts")
     return counts
 
+
+# ---- set criterion (criterion.py): matching costs and point-sampled mask losses of every prediction of one call ----
+def _device_table(values, dev):
+    """int64 table (pointers, offsets) -> device, by a pinned host-to-device copy (no sync)."""
+    host = torch.tensor(values, dtype=torch.int64).pin_memory()
+    return host.to(dev, non_blocking=True)
+
+
+def _check_preds(tensors, name, ndim):
+    if not tensors:
+        raise RuntimeError(f"{name}: at least one prediction is needed")
+    for i, t in enumerate(tensors):
+        _c(t, f"{name}[{i}]")
+        if t.dim() != ndim or t.shape != tensors[0].shape or t.device != tensors[0].device:
+            raise RuntimeError(f"{name}[{i}]: shape {tuple(t.shape)} / {t.device} differs from {name}[0] "
+                               f"{tuple(tensors[0].shape)} / {tensors[0].device}")
+
+
+def _check_targets(tgt, dev):
+    _c(tgt, "tgt_masks", torch.uint8)
+    if tgt.dim() != 3 or tgt.device != dev:
+        raise RuntimeError(f"tgt_masks must be (T, Hg, Wg) uint8 on {dev}, got {tuple(tgt.shape)} on {tgt.device}")
+
+
+def match_cost(logits, masks, tgt_masks, labels, toff, points, w_class=1.0, w_mask=1.0, w_dice=1.0):
+    """The matcher's cost matrices of every (prediction, image) in one launch (msm_match_cost).  logits: list of (B,Q,C+1),
+    masks: list of (B,Q,Hm,Wm) fp32 (one entry per prediction, not stacked), tgt_masks (T,Hg,Wg) uint8 0/1 targets of the
+    whole batch, labels (T,) int32, toff: B + 1 host ints (image b's targets are rows toff[b]..toff[b+1]), points
+    (n_pred,B,P,2) -> cost (n_pred,Q,T): image b's matrix is cost[:, :, toff[b]:toff[b+1]]."""
+    _check_preds(logits, "logits", 3), _check_preds(masks, "masks", 4)
+    dev = masks[0].device
+    n_pred = len(masks)
+    B, Q, C1 = logits[0].shape
+    _, _, Hm, Wm = masks[0].shape
+    if len(logits) != n_pred or masks[0].shape[:2] != (B, Q) or logits[0].device != dev:
+        raise RuntimeError("match_cost: logits and masks must be per-prediction lists of (B,Q,C+1) / (B,Q,Hm,Wm)")
+    _check_targets(tgt_masks, dev)
+    _c(labels, "labels", torch.int32), _c(points, "points")
+    toff = [int(v) for v in toff]
+    TT = tgt_masks.shape[0]
+    if len(toff) != B + 1 or toff[0] != 0 or toff[-1] != TT or any(b < a for a, b in zip(toff, toff[1:])):
+        raise RuntimeError(f"match_cost: toff {toff} does not partition {TT} targets over {B} images")
+    if labels.shape != (TT,) or points.dim() != 4 or points.shape[:2] != (n_pred, B) or points.shape[3] != 2:
+        raise RuntimeError(f"match_cost: labels {tuple(labels.shape)} / points {tuple(points.shape)} do not fit")
+    P = points.shape[2]
+    max_T = max([b - a for a, b in zip(toff, toff[1:])] + [0])
+    cost = torch.empty((n_pred, Q, TT), device=dev, dtype=torch.float32)
+    table = _device_table([t.data_ptr() for t in logits] + [t.data_ptr() for t in masks] + toff, dev)
+    check(lib().msm_match_cost(_p(table), _p(tgt_masks), _p(labels), _p(points), _p(cost), n_pred, B, Q, C1, Hm, Wm,
+                               tgt_masks.shape[1], tgt_masks.shape[2], P, TT, max_T, float(w_class), float(w_mask),
+                               float(w_dice), _stream()), "msm_match_cost")
+    return cost
+
+
+def _point_loss_args(masks, tgt_masks, pairs, os_points, rnd_points, k):
+    _check_preds(masks, "masks", 4)
+    dev = masks[0].device
+    _check_targets(tgt_masks, dev)
+    _c(pairs, "pairs", torch.int32), _c(os_points, "os_points"), _c(rnd_points, "rnd_points")
+    n_pred = len(masks)
+    B, Q, Hm, Wm = masks[0].shape
+    N = os_points.shape[1] if os_points.dim() == 4 else -1
+    Pos = os_points.shape[2] if os_points.dim() == 4 else -1
+    if (os_points.dim() != 4 or os_points.shape[0] != n_pred or os_points.shape[3] != 2 or rnd_points.dim() != 4
+            or rnd_points.shape[:2] != (n_pred, N) or rnd_points.shape[3] != 2 or pairs.shape != (n_pred * N, 4)):
+        raise RuntimeError(f"point_loss: os_points {tuple(os_points.shape)}, rnd_points {tuple(rnd_points.shape)} and pairs "
+                           f"{tuple(pairs.shape)} must be (n_pred,N,Pos,2), (n_pred,N,P-k,2), (n_pred*N,4)")
+    P = int(k) + rnd_points.shape[2]
+    if not 0 <= int(k) <= Pos:
+        raise RuntimeError(f"point_loss: k={k} outside [0, {Pos}]")
+    return dev, n_pred, N, B * Q, Hm, Wm, Pos, P
+
+
+def point_loss_workspace_bytes(n_pairs, k):
+    return int(lib().msm_point_loss_workspace(int(n_pairs), int(k)))
+
+
+def point_loss_fwd(masks, tgt_masks, pairs, os_points, rnd_points, k, num_masks):
+    """loss_masks of every prediction in one pass (msm_point_loss_fwd): masks list of (B,Q,Hm,Wm) fp32, tgt_masks (T,Hg,Wg)
+    uint8, pairs (n_pred*N,4) int32 rows (prediction, n, b*Q+q, target row), os_points (n_pred,N,Pos,2), rnd_points
+    (n_pred,N,P-k,2), k selected points per mask -> (losses (2,n_pred) = loss_mask, loss_dice; sel_bits (n_pred*N,
+    ceil(Pos/32)) int32 selection bitmaps; workspace for point_loss_bwd)."""
+    dev, n_pred, N, BQ, Hm, Wm, Pos, P = _point_loss_args(masks, tgt_masks, pairs, os_points, rnd_points, k)
+    n_pairs = n_pred * N
+    losses = torch.empty((2, n_pred), device=dev, dtype=torch.float32)
+    bits = torch.empty((n_pairs, (Pos + 31) // 32), device=dev, dtype=torch.int32)
+    nbytes = point_loss_workspace_bytes(n_pairs, k)
+    ws = torch.empty((max(1, nbytes // 4),), device=dev, dtype=torch.int32)
+    table = _device_table([t.data_ptr() for t in masks], dev)
+    check(lib().msm_point_loss_fwd(_p(table), _p(tgt_masks), _p(pairs), _p(os_points), _p(rnd_points), _p(losses), _p(bits),
+                                   _p(ws), nbytes, n_pred, N, BQ, tgt_masks.shape[0], Hm, Wm, tgt_masks.shape[1],
+                                   tgt_masks.shape[2], Pos, int(k), P, float(num_masks), _stream()), "msm_point_loss_fwd")
+    return losses, bits, ws
+
+
+def point_loss_bwd(masks, tgt_masks, pairs, os_points, rnd_points, workspace, grad_losses, k, num_masks, global_atomics=False):
+    """Gradient of point_loss_fwd's losses (msm_point_loss_bwd): grad_losses (2,n_pred) -> list of (B,Q,Hm,Wm) gradients, zero
+    outside the matched masks.  global_atomics forces the global float-atomic scatter (the path of masks above 128 KiB)."""
+    dev, n_pred, N, BQ, Hm, Wm, Pos, P = _point_loss_args(masks, tgt_masks, pairs, os_points, rnd_points, k)
+    _c(grad_losses, "grad_losses")
+    _c(workspace, "workspace", torch.int32)
+    if grad_losses.shape != (2, n_pred):
+        raise RuntimeError(f"point_loss_bwd: grad_losses {tuple(grad_losses.shape)} must be (2, {n_pred})")
+    grads = [torch.zeros_like(m) for m in masks]
+    nbytes = point_loss_workspace_bytes(n_pred * N, k)
+    if workspace.numel() * 4 < nbytes:
+        raise RuntimeError(f"point_loss_bwd: workspace of {workspace.numel() * 4} bytes, {nbytes} needed")
+    table = _device_table([t.data_ptr() for t in masks] + [t.data_ptr() for t in grads], dev)
+    check(lib().msm_point_loss_bwd(_p(table), _p(tgt_masks), _p(pairs), _p(os_points), _p(rnd_points), _p(workspace), nbytes,
+                                   _p(grad_losses), n_pred, N, BQ, tgt_masks.shape[0], Hm, Wm, tgt_masks.shape[1],
+                                   tgt_masks.shape[2], Pos, int(k), P, float(num_masks), 1 if global_atomics else 0,
+                                   _stream()), "msm_point_loss_bwd")
+    return grads
+
 def label_image(masks, inst_labels):
     """masks (B,K,H,W) float (non-zero = inside), inst_labels (B,K) float -> (B,H,W) float label images (msm_label_image)."""
     _c(masks, "masks"), _c(inst_labels, "inst_labels")

@@ -376,3 +376,42 @@ def synth_label_pair(H, W, seed, kind="blobs", n_gt=8, n_pred=8, gt_values=None,
     else:
         raise ValueError(kind)
     return pred, gt
+
+
+def synth_criterion_inputs(n_pred=10, B=3, T=(0, 17, 4), Q=100, C1=3, hm=60, wm=80, hg=240, wg=320, seed=0):
+    """Seeded inputs of the set criterion (criterion.SetCriterion): (outputs, targets) with outputs = {"pred_logits" (B,Q,C1),
+    "pred_masks" (B,Q,hm,wm), "aux_outputs": n_pred - 1 more such dicts} and targets = B dicts {"labels" (T_b,) int64 in
+    [0, C1 - 1), "masks" (T_b,hg,wg) bool}.  Target masks are planted rectangles / ellipses; in every prediction target t of
+    image b has a planted query (a fixed random permutation) whose logits are +4 inside the target (at mask resolution) and -4
+    outside, plus noise that grows towards the earlier predictions; the other queries are negative blobs.  Class logits of the
+    planted queries favour the target's label, the others the no-object class.  Costs therefore have clear minima."""
+    rng = np.random.default_rng(7000 + seed)
+    targets, planted = [], []
+    for b in range(B):
+        masks = np.zeros((T[b], hg, wg), dtype=bool)
+        for t in range(T[b]):
+            img = np.zeros((hg, wg), dtype=np.int64)
+            _plant(img, rng, 1 + t % 2, [1, 1], hg, wg)
+            masks[t] = img > 0
+        labels = rng.integers(0, C1 - 1, size=T[b])
+        targets.append({"labels": torch.from_numpy(labels.astype(np.int64)), "masks": torch.from_numpy(masks)})
+        planted.append(rng.permutation(Q)[:min(Q, T[b])])
+    yy = (np.arange(hm) + 0.5) * hg / hm
+    xx = (np.arange(wm) + 0.5) * wg / wm
+    iy, ix = np.clip(yy.astype(np.int64), 0, hg - 1), np.clip(xx.astype(np.int64), 0, wg - 1)
+    preds = []
+    for p in range(n_pred):
+        noise = 0.5 + 0.15 * (n_pred - 1 - p)
+        logits = rng.normal(0.0, 0.5, size=(B, Q, C1)).astype(np.float32)
+        logits[:, :, C1 - 1] += 2.0
+        masks = -4.0 + rng.normal(0.0, noise, size=(B, Q, hm, wm))
+        for b in range(B):
+            for t, q in enumerate(planted[b]):
+                tm = targets[b]["masks"].numpy()[t][np.ix_(iy, ix)]
+                masks[b, q] = np.where(tm, 4.0, -4.0) + rng.normal(0.0, noise, size=(hm, wm))
+                logits[b, q, C1 - 1] -= 3.0
+                logits[b, q, int(targets[b]["labels"][t])] += 2.0
+        preds.append({"pred_logits": torch.from_numpy(logits), "pred_masks": torch.from_numpy(masks.astype(np.float32))})
+    outputs = dict(preds[-1])
+    outputs["aux_outputs"] = preds[:-1]
+    return outputs, targets

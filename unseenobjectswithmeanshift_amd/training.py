@@ -205,3 +205,14 @@ def decoder_forward_train(dec, x, mask_features):
         pred_mask.append(mask)
     return {"pred_logits": pred_cls[-1], "pred_masks": pred_mask[-1],
             "aux_outputs": [{"pred_logits": a, "pred_masks": b} for a, b in zip(pred_cls[:-1], pred_mask[:-1])]}
+
+
+def weighted_losses(losses, weight_dict):
+    """meanshiftformer_model.py:279-285: every loss with a weight in ``weight_dict`` times that weight; the others dropped."""
+    return {k: v * weight_dict[k] for k, v in losses.items() if k in weight_dict}
+
+
+def decoder_losses(dec, x, mask_features, targets, criterion):
+    """decoder_forward_train -> criterion (criterion.SetCriterion) -> weighted_losses: the weighted loss dict of one training
+    step of the decoder; ``sum(decoder_losses(...).values()).backward()`` runs every backward on the HIP kernels."""
+    return weighted_losses(criterion(decoder_forward_train(dec, x, mask_features), targets), criterion.weight_dict)
