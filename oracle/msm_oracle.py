@@ -37,16 +37,17 @@ EMBEDDING_ALPHA = 0.02  # lib/fcn/config.py:255 (epsilon = 2*alpha, MS:123)
 # position encoding (PE:12-52)
 # ----------------------------------------------------------------------------------------------
 def position_embedding_sine(batch, height, width, num_pos_feats, temperature=10000.0,
-                            scale=2.0 * math.pi):
+                            scale=2.0 * math.pi, dtype=torch.float32):
     """normalize=True variant used by both decoders (DEC:414-415, MSD:240-241).
     Returns (batch, 2*num_pos_feats, H, W): first half is the y code, second half the x code,
-    channels interleave sin (even) / cos (odd) (PE:43-50)."""
+    channels interleave sin (even) / cos (odd) (PE:43-50).  ``dtype=torch.float64`` evaluates the
+    same definition in double (the yardstick of tests/test_gpu_norm.py)."""
     eps = 1e-6
-    ys = torch.arange(1, height + 1, dtype=torch.float32)      # cumsum of ones (PE:33)
-    xs = torch.arange(1, width + 1, dtype=torch.float32)
+    ys = torch.arange(1, height + 1, dtype=dtype)              # cumsum of ones (PE:33)
+    xs = torch.arange(1, width + 1, dtype=dtype)
     ys = ys / (ys[-1] + eps) * scale                           # PE:37
     xs = xs / (xs[-1] + eps) * scale
-    i = torch.arange(num_pos_feats, dtype=torch.float32)
+    i = torch.arange(num_pos_feats, dtype=dtype)
     dim_t = temperature ** (2 * torch.div(i, 2, rounding_mode="floor") / num_pos_feats)  # PE:41
     py = ys[:, None] / dim_t                                   # (H, N)
     px = xs[:, None] / dim_t                                   # (W, N)
@@ -58,7 +59,7 @@ def position_embedding_sine(batch, height, width, num_pos_feats, temperature=100
         return out
 
     py, px = interleave(py), interleave(px)
-    pos = torch.empty(2 * num_pos_feats, height, width, dtype=torch.float32)
+    pos = torch.empty(2 * num_pos_feats, height, width, dtype=dtype)
     pos[:num_pos_feats] = py.t()[:, :, None]
     pos[num_pos_feats:] = px.t()[:, None, :]
     return pos[None].expand(batch, -1, -1, -1).contiguous()
@@ -516,3 +517,63 @@ def instance_inference(mask_cls, mask_pred_lowres, image_size, topk=20, padded_s
     mscore = (m.sigmoid().flatten(1) * binm.flatten(1)).sum(1) / (binm.flatten(1).sum(1) + 1e-6)
     return {"pred_masks": binm, "pred_boxes": mask_boxes(m > 0), "scores": s * mscore,
             "pred_classes": classes, "query_index": idx // K}
+
+
+# ----------------------------------------------------------------------------------------------
+# float64 definitions of the normalisation operations (yardsticks of tests/test_gpu_norm.py; written from the
+# mathematical definitions, checked against torch's own double kernels in tests/test_norm_defs_cpu.py)
+# ----------------------------------------------------------------------------------------------
+def _ln64(v, g, b, eps):
+    mean = v.mean(-1, keepdim=True)
+    var = ((v - mean) ** 2).mean(-1, keepdim=True)             # two-pass, biased
+    return (v - mean) / torch.sqrt(var + eps) * g.double() + b.double()
+
+
+def layernorm_chain(x, parts, bias, g1, b1, l2norm=False, g2=None, b2=None, eps=1e-5):
+    """LN(x + sum(parts) + bias) [/ max(||.||_2, 1e-12)] [-> a second LN], all in float64.  x (..., E) or None, parts
+    (n, ..., E) or None, bias (E,) or None.  Returns (y, y2); y2 is None without g2."""
+    v = x.double() if x is not None else torch.zeros(parts.shape[1:], dtype=torch.float64)
+    if parts is not None:
+        v = v + parts.double().sum(0)
+    if bias is not None:
+        v = v + bias.double()
+    y = _ln64(v, g1, b1, eps)
+    if l2norm:
+        y = y / torch.sqrt((y * y).sum(-1, keepdim=True)).clamp_min(1e-12)
+    return y, (_ln64(y, g2, b2, eps) if g2 is not None else None)
+
+
+def bilinear_upsample_tokens(up, up_hw, H, W):
+    """align_corners=False bilinear resize of a token map up (B, uh*uw, C) to (B, H*W, C) in float64, from the
+    definition: source coordinate max(0, (dst + 0.5) * in / out - 0.5), lower neighbour its floor, upper neighbour
+    clamped to in - 1, weights the fractional part."""
+    uh, uw = up_hw
+    B, _, C = up.shape
+    u = up.double().reshape(B, uh, uw, C)
+
+    def taps(out, n):
+        src = ((torch.arange(out, dtype=torch.float64) + 0.5) * n / out - 0.5).clamp_min(0.0)
+        i0 = src.floor().long().clamp_max(n - 1)
+        i1 = (i0 + 1).clamp_max(n - 1)
+        return i0, i1, src - i0
+
+    y0, y1, ly = taps(H, uh)
+    x0, x1, lx = taps(W, uw)
+    ly, lx = ly[None, :, None, None], lx[None, None, :, None]
+    top = u[:, y0][:, :, x0] * (1 - lx) + u[:, y0][:, :, x1] * lx
+    bot = u[:, y1][:, :, x0] * (1 - lx) + u[:, y1][:, :, x1] * lx
+    return (top * (1 - ly) + bot * ly).reshape(B, H * W, C)
+
+
+def groupnorm_tokens(x, gamma, beta, H, W, groups=32, eps=1e-5, up=None, up_hw=None, relu=False):
+    """GroupNorm over an NHWC token map x (B, H*W, C) in float64 (two-pass mean and biased variance per (image, group)
+    over H*W * C/groups values) [+ bilinear_upsample_tokens(up)] [-> ReLU].  Returns (B, H*W, C) float64."""
+    B, HW, C = x.shape
+    assert HW == H * W and C % groups == 0
+    v = x.double().reshape(B, HW, groups, C // groups)
+    mean = v.mean((1, 3), keepdim=True)
+    var = ((v - mean) ** 2).mean((1, 3), keepdim=True)
+    y = ((v - mean) / torch.sqrt(var + eps)).reshape(B, HW, C) * gamma.double() + beta.double()
+    if up is not None:
+        y = y + bilinear_upsample_tokens(up, up_hw, H, W)
+    return y.clamp_min(0.0) if relu else y

@@ -14,6 +14,15 @@
 
 namespace msm {
 
+// Pairwise sum of a lane's N = 2^k values.  Together with the butterfly of wave_sum the whole row is summed as a balanced tree:
+// a constant row adds equal terms at every level, which is exact, so its mean is the constant itself and the result is b1 --
+// a sequential sum of eight equal terms is not (3c, 5c, 6c, 7c round), and rstd <= 1/sqrt(eps) multiplies what is left by 316.
+template <int N>
+__device__ __forceinline__ float tree_sum(const float* v) {
+    if constexpr (N == 1) return v[0];
+    else return tree_sum<N / 2>(v) + tree_sum<N / 2>(v + N / 2);
+}
+
 template <int VPT>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ parts,
                                                         int n_parts, int64_t part_stride,
@@ -37,10 +46,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         v[i] = t;
     }
     auto ln = [&](const float* __restrict__ g, const float* __restrict__ b) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) s += v[i];
-        const float mean = wave_sum(s) * (1.0f / E);
+        const float mean = wave_sum(tree_sum<VPT>(v)) * (1.0f / E);
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -75,9 +81,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 // ---- GroupNorm --------------------------------------------------------------------------------
 // stats[b][c] = (sum, sumsq) in double.  Thread = (4 consecutive channels, pixel stream): 16-byte
-// loads, fp32 partial sums over a short run of pixels, then double for the cross-thread reduction and
-// one double atomic per (block, channel).  Double accumulation keeps E[x^2]-E[x]^2 well conditioned and
-// makes the result insensitive to the (unordered) atomic arrival order at fp32 precision.
+// loads, every value widened to double BEFORE it is squared and added (the square of an fp32 is exact in
+// double), double for the cross-thread reduction and one double atomic per (block, channel).  Nothing is
+// rounded to fp32 on the way, so E[x^2]-E[x]^2 in the apply kernels stays well conditioned for maps whose
+// mean is large against their spread (a biased 1x1 convolution in front), and the result is insensitive to
+// the (unordered) atomic arrival order at fp32 precision.  The kernel streams from HBM: the 3 fp64
+// operations per element are hidden behind the loads.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, double* __restrict__ stats,
                                                        int HW, int C, int pix_per_block) {
     const int b = blockIdx.y;
@@ -86,20 +95,24 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     const int c4n = C >> 2;                    // float4 per pixel
     const int streams = 256 / c4n;
     const int c4 = threadIdx.x % c4n, st = threadIdx.x / c4n;
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
     if (st < streams) {
         const float* xb = x + ((int64_t)b * HW) * C + c4 * 4;
         for (int p = p0 + st; p < p1; p += streams) {
             const float4 v = *reinterpret_cast<const float4*>(xb + (int64_t)p * C);
-            s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
-            q[0] += v.x * v.x; q[1] += v.y * v.y; q[2] += v.z * v.z; q[3] += v.w * v.w;
+            const double d[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s[e] += d[e];
+                q[e] = fma(d[e], d[e], q[e]);
+            }
         }
     }
     __shared__ double red[2][4][256];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        red[0][e][threadIdx.x] = (double)s[e];
-        red[1][e][threadIdx.x] = (double)q[e];
+        red[0][e][threadIdx.x] = s[e];
+        red[1][e][threadIdx.x] = q[e];
     }
     __syncthreads();
     if (threadIdx.x < C) {
