@@ -3,12 +3,17 @@
 torch is used for device memory and streams only: every function checks its arguments, allocates
 the outputs with torch.empty on the inputs' device and launches the HIP kernels of libmsm_hip.so
 on torch's current stream.  Tensors must be fp32 and live on a ROCm device; there is no CPU path.
+The weight layouts that need no launch (pack_encoder_block*, pack_conv_in_weight*, ...) are packing.py's, re-exported here.
 """
 import ctypes
 
 import torch
 
 from ._lib import check, lib
+from .packing import (MASK_CONV_K, MASK_CONV_LD, PROJ_REC_FLOATS, dense_kv_constant, mask_conv_fold_weight, pack_conv_in_weight,  # noqa: F401
+                      pack_conv_in_weight_lp, pack_encoder_block, pack_encoder_block_hm, pack_encoder_block_hm_small,
+                      pack_encoder_block_lp, pack_encoder_block_split, pack_encoder_prologue, pack_encoder_prologue_hm,
+                      pack_msda_proj_lp, proj_records_to_columns, proj_to_head_major_records)
 
 KAPPA = 30.0  # attention_util.py:26
 
@@ -99,27 +104,6 @@ def conv1x1_nchw_to_tokens(x, w, bias=None):
     return out
 
 
-def pack_conv_in_weight(w):
-    """(64, Cin) 1x1-convolution weight -> the fragment order msm_conv1x1_in_f32 reads (include/msm_hip.h):
-    packed[(((k//8)*4 + o//16)*64 + ((k%8)//2)*16 + o%16)*2 + k%2] = w[o][k]."""
-    O, Cin = w.shape
-    if O != 64 or Cin % 8:
-        raise RuntimeError("pack_conv_in_weight needs a (64, Cin) weight with Cin a multiple of 8")
-    return w.reshape(4, 16, Cin // 8, 4, 2).permute(2, 0, 3, 1, 4).contiguous().reshape(-1)
-
-
-def pack_conv_in_weight_lp(w):
-    """(64, Cin) weight -> the hi + lo bf16 fragment order msm_conv1x1_in_lp reads (include/msm_hip.h):
-    packed[g][o//16][plane][(k%32)//8][o%16][k%8] = plane(w)[o][k], g = k//32, plane 0 = bf16(w), plane 1 = bf16(w - plane 0)."""
-    O, Cin = w.shape
-    if O != 64 or Cin % 256:
-        raise RuntimeError("pack_conv_in_weight_lp needs a (64, Cin) weight with Cin a multiple of 256")
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
-    planes = torch.stack([hi, lo])                                                   # (2, 64, Cin)
-    return planes.reshape(2, 4, 16, Cin // 32, 4, 8).permute(3, 1, 0, 4, 2, 5).contiguous().reshape(-1)
-
-
 def conv1x1_in(x, w_packed, bias=None, *, out=None, stats=None, stats_cleared=False, lp=False):
     """Input projection of the pixel decoder: x (B, Cin, H, W) NCHW, w_packed = pack_conv_in_weight(w (64, Cin)) ->
     tokens (B, H*W, 64) = x^T w^T + bias  (``lp``: w_packed = pack_conv_in_weight_lp(w), hi + lo bf16 operands on the bf16
@@ -189,14 +173,6 @@ def is_token_major(x):
         return False
     B, C, H, W = x.shape
     return x.stride(1) == 1 and x.stride(3) == C and x.stride(2) == W * C and x.stride(0) >= H * W * C and C > 1
-
-
-def dense_kv_constant(cmat, cmat_width):
-    """The (H*W, N) matrix of a separable constant [(H row vectors | W column vectors), N] (cmat_width = W; 0: cmat itself)."""
-    if not cmat_width:
-        return cmat
-    h = cmat.shape[0] - cmat_width
-    return (cmat[:h, None, :] + cmat[None, h:, :]).reshape(h * cmat_width, cmat.shape[1]).contiguous()
 
 
 def kv_project(x, w, cmat, cmat_width=0):
@@ -658,24 +634,6 @@ def tokens_f16(x):
     out = torch.empty((B, H * W, C), device=x.device, dtype=torch.float16)
     check(lib().msm_nchw_to_tokens_f16(_p(x), _p(out), B, C, H * W, _stream()), "msm_nchw_to_tokens_f16")
     return out
-
-
-MASK_CONV_K = 576            # 9 taps x 64 channels; column 576 of a folded filter row is the per-query constant
-MASK_CONV_LD = 580           # row length of mask_conv_fold_weight's GEMM output (16-byte aligned rows)
-
-
-def mask_conv_fold_weight(weight, bias=None):
-    """Conv2d(64, Cm, 3, padding=1) weight (Cm, 64, 3, 3) [+ bias (Cm,)] -> the (580, Cm) matrix Wf with
-    gemm(e, Wf)[b, q] = [F[b, q, 64 * (3 ky + kx) + c] = sum_o e[b, q, o] W[o, c, ky, kx] | e[b, q, :] . bias | 0 0 0]:
-    the per-query 3x3 filters mask_conv3x3_folded convolves the 64-channel feature with (the convolution folded into the embedding)."""
-    Cm, C, kh, kw = weight.shape
-    if (C, kh, kw) != (64, 3, 3):
-        raise RuntimeError("mask_conv_fold_weight: a (Cm, 64, 3, 3) convolution weight")
-    wf = torch.zeros((MASK_CONV_LD, Cm), device=weight.device, dtype=torch.float32)
-    wf[:MASK_CONV_K] = weight.detach().float().permute(2, 3, 1, 0).reshape(MASK_CONV_K, Cm)
-    if bias is not None:
-        wf[MASK_CONV_K] = bias.detach().float()
-    return wf
 
 
 def mask_conv3x3_folded(x_f16, F, size, *, bits=True, row_any=None):
@@ -1279,46 +1237,6 @@ def instance_postprocess(mask_logits, query_index, image_size, class_scores=None
     return masks, score, boxes
 
 
-def pack_encoder_prologue(wv, wp):
-    """Weight stream of msm_encoder_prologue_fwd: value_proj (64,64) then [sampling_offsets | attention_weights]
-    (proj_width,64) as consecutive 16-row blocks, zero-padded to the stream length."""
-    pw = wp.shape[0]
-    n = int(lib().msm_encoder_prologue_stream_floats(pw))
-    out = torch.zeros(n, device=wv.device, dtype=torch.float32)
-    out[:64 * 64] = wv.reshape(-1)
-    out[64 * 64:64 * 64 + pw * 64] = wp.reshape(-1)
-    return out
-
-
-def encoder_prologue(raw, stats, gn_params, level_starts, stream, small, pos, proj_width, *, groups=32, eps=1e-5, value_heads=0,
-                     bf16_hm=False):
-    """raw (B,S,64) concatenated input projections (conv1x1_in), stats (L,B,64,2) float64 their GroupNorm moments,
-    gn_params (L,2,64) = gamma, beta, level_starts: L+1 token offsets (0..S).  Normalises raw IN PLACE (-> src) and
-    returns (src, value, proj) for the first encoder layer: value (B,S,64) or head-major (B,heads,S,64/heads),
-    proj (B,S,proj_width) = [sampling_offsets | attention_weights](src + pos).  bf16_hm (8 heads, proj_width 288): value and
-    proj are the bf16 plan's head-major fp16 tensors (B,8,S,8) and (B,8,S,36) (encoder_block_hm)."""
-    _c(raw, "raw"), _c(stats, "stats", torch.float64), _c(gn_params, "gn_params"), _c(stream, "stream"), _c(small, "small"), _c(pos, "pos")
-    B, S, C = raw.shape
-    L = len(level_starts) - 1
-    if C != 64 or tuple(stats.shape) != (L, B, 64, 2) or tuple(gn_params.shape) != (L, 2, 64) or tuple(pos.shape) != (S, 64):
-        raise RuntimeError("encoder_prologue: inconsistent shapes")
-    if small.numel() != 64 + proj_width:
-        raise RuntimeError("encoder_prologue: small must hold the 64 value_proj biases and the proj_width projection biases")
-    dev = raw.device
-    if bf16_hm:
-        value = torch.empty((B, 8, S, 8), device=dev, dtype=torch.float16)
-        proj = torch.empty((B, 8, S, PROJ_REC_FLOATS), device=dev, dtype=torch.float32)
-    else:
-        value = torch.empty((B, value_heads, S, 64 // value_heads) if value_heads else (B, S, 64), device=dev, dtype=torch.float32)
-        proj = torch.empty((B, S, proj_width), device=dev, dtype=torch.float32) if proj_width else None     # 0: value projection only
-    ls = (ctypes.c_int32 * (L + 1))(*[int(v) for v in level_starts])
-    rc = lib().msm_encoder_prologue_fwd(_p(raw), _p(stats), _p(gn_params), ctypes.cast(ls, ctypes.c_void_p), L, int(groups), float(eps),
-                                        _p(stream), _p(small), _p(pos), _p(raw), _p(value), _p(proj), B, S, int(proj_width),
-                                        int(value_heads), int(bool(bf16_hm)), _stream())
-    check(rc, "msm_encoder_prologue_fwd")
-    return raw, value, proj
-
-
 def label_stats(labels, weight=None, k=1024):
     """labels (B,H,W) float32 with integer values in [0,k), weight (B,H,W) float32 or None ->
     (stats (B,k,5) int32 = area, x_min, y_min, x_max, y_max; wsum (B,k) float32; overflow (B,) int32)."""
@@ -1469,6 +1387,7 @@ def point_loss_bwd(masks, tgt_masks, pairs, os_points, rnd_points, workspace, gr
                                    _stream()), "msm_point_loss_bwd")
     return grads
 
+
 def label_image(masks, inst_labels):
     """masks (B,K,H,W) float (non-zero = inside), inst_labels (B,K) float -> (B,H,W) float label images (msm_label_image)."""
     _c(masks, "masks"), _c(inst_labels, "inst_labels")
@@ -1504,300 +1423,8 @@ def paste_labels(renum, table, order, frame_start, frames, H, W):
 
 
 # ----------------------------------------------------------------------------------------------
-# fused encoder block (msdeformattn.py:122-131)
+# backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------
-def pack_encoder_block(wo, w1, w2, wv=None, wp=None):
-    """Pack one encoder layer's matrices into the weight stream consumed by msm_encoder_block_fwd.
-
-    Stream = chunks of 8 blocks, one block = 1024 floats (4 KiB):
-      chunk 0            : output_proj  -- 4 row blocks [16 out rows][64 k] (+4 zero blocks)
-      chunks 1..d_ffn/64 : 4 x ( linear1 row block [16 hidden rows][64 k] , linear2 block [64 out rows][16 hidden] )
-      then (only with the next layer's wv/wp): value_proj 4 row blocks, then [offsets|weights] row blocks,
-      continuing into further chunks of 8.
-    A "row block" is 16 consecutive rows of a (N, 64) weight; the kernel applies the LDS swizzle itself."""
-    dev = wo.device
-    d_ffn = w1.shape[0]
-    blocks = [wo.reshape(4, 1024)] + [torch.zeros(4, 1024, device=dev)]
-    w1b = w1.reshape(d_ffn // 16, 1024)                                                # (hb, 16 rows * 64 k)
-    w2b = w2.reshape(64, d_ffn // 16, 16).permute(1, 0, 2).reshape(d_ffn // 16, 1024)    # (hb, 64 rows * 16 k)
-    blocks.append(torch.stack([w1b, w2b], 1).reshape(-1, 1024))                        # interleaved per hb
-    if wv is not None:
-        npb = wp.shape[0] // 16
-        tail = torch.cat([wv.reshape(4, 1024), wp.reshape(npb, 1024)], 0)
-        pad = (-tail.shape[0]) % 8
-        blocks += [tail, torch.zeros(pad, 1024, device=dev)]
-    return torch.cat(blocks, 0).reshape(-1).contiguous()
-
-
-def pack_encoder_block_split(wo, w1, w2, wv=None, wp=None):
-    """One encoder layer's matrices as the triple-split weight stream of msm_encoder_block_split_fwd (include/msm_hip.h):
-    every fp32 weight as w = h + m + l with h = bf16(w), m = bf16(w - h), l = bf16(w - h - m); 2-KiB blocks in the fragment
-    order of v_mfma_f32_16x16x32_bf16, a logical block = its (h, m, l) blocks, 12 blocks per stage.
-    Returns an int16 tensor (bf16 bit patterns)."""
-    dev = wo.device
-    d_ffn = w1.shape[0]
-
-    def rowblocks(w):       # (N, 64) -> (N/16, 1024): block[G][lq][lj][hh][c] = W[r0 + lj][(2G + hh)*16 + lq*4 + c]
-        return w.reshape(-1, 16, 2, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(-1, 1024)
-
-    def w2pairs(w):         # (64, d_ffn) -> (d_ffn/32, 2048): [ob][lq][lj][hh][c] = W[ob*16 + lj][(2P + hh)*16 + lq*4 + c]
-        return w.reshape(4, 16, d_ffn // 32, 2, 4, 4).permute(2, 0, 4, 1, 3, 5).reshape(-1, 2048)
-
-    def split3(w):
-        h = w.to(torch.bfloat16).float()
-        m = (w - h).to(torch.bfloat16).float()
-        return h, m, (w - h - m).to(torch.bfloat16).float()
-
-    def triples(parts):                                   # three (n, k) lists -> (n, 3k) as [h | m | l] per logical block
-        return torch.cat(list(parts), 1)
-
-    w1t = triples(rowblocks(t) for t in split3(w1)).reshape(d_ffn // 32, 2 * 3 * 1024)        # per stage: W1(q0) h,m,l | W1(q1) h,m,l
-    w2t = triples(w2pairs(t) for t in split3(w2))                                            # per stage: W2 h | m | l (4 KiB each)
-    blocks = [triples(rowblocks(t) for t in split3(wo)).reshape(-1), torch.cat([w1t, w2t], 1).reshape(-1)]
-    if wv is not None:
-        blocks.append(triples(rowblocks(t) for t in split3(wv)).reshape(-1))
-        pt = triples(rowblocks(t) for t in split3(wp)).reshape(-1)
-        blocks += [pt, torch.zeros((-(pt.numel() // 1024)) % 12 * 1024, device=dev)]
-    out = torch.cat(blocks, 0).to(torch.bfloat16).contiguous().view(torch.int16).reshape(-1)
-    need = int(lib().msm_encoder_block_split_stream_bytes(d_ffn, 0 if wp is None else wp.shape[0]))
-    if out.numel() * 2 != need:
-        raise RuntimeError(f"pack_encoder_block_split: built {out.numel() * 2} bytes, the kernel expects {need}")
-    return out
-
-
-def pack_encoder_block_lp(wo, w1, w2, wv=None, wp=None):
-    """One encoder layer's matrices as the weight stream of msm_encoder_block_lp_fwd (include/msm_hip.h): the low-precision
-    mode on the K = 32 kernel -- projections as [h, m] bf16 pairs, linear1 / linear2 as single bf16 copies, three hidden pairs
-    per 12-block stage.  Returns an int16 tensor (bf16 bit patterns)."""
-    dev = wo.device
-    d_ffn = w1.shape[0]
-
-    def rowblocks(w):       # (N, 64) -> (N/16, 1024): block[G][lq][lj][hh][c] = W[r0 + lj][(2G + hh)*16 + lq*4 + c]
-        return w.reshape(-1, 16, 2, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(-1, 1024)
-
-    def w2pairs(w):         # (64, d_ffn) -> (d_ffn/32, 2048): [ob][lq][lj][hh][c] = W[ob*16 + lj][(2P + hh)*16 + lq*4 + c]
-        return w.reshape(4, 16, d_ffn // 32, 2, 4, 4).permute(2, 0, 4, 1, 3, 5).reshape(-1, 2048)
-
-    def hm(w):
-        h = w.to(torch.bfloat16).float()
-        return h, (w - h).to(torch.bfloat16).float()
-
-    def proj_stage_blocks(w, per_stage):                  # [h, m] per row block, zero padded to whole 12-block stages
-        h, m = (rowblocks(t) for t in hm(w))
-        t = torch.stack([h, m], 1).reshape(-1, 1024)
-        pad = (-t.shape[0]) % (2 * per_stage) if per_stage * 2 == 12 else (12 - t.shape[0] % 12) % 12
-        return torch.cat([t, torch.zeros(pad, 1024, device=dev)], 0)
-
-    npair = d_ffn // 32
-    w1h = rowblocks(w1.to(torch.bfloat16).float()).reshape(npair, 2048)            # W1(q0) | W1(q1) of a pair
-    w2h = w2pairs(w2.to(torch.bfloat16).float())                                    # (npair, 2048)
-    ffn = torch.cat([w1h, w2h], 1)                                                  # (npair, 4 blocks)
-    ffn = torch.cat([ffn, torch.zeros((-npair) % 3, 4096, device=dev)], 0).reshape(-1)
-    blocks = [proj_stage_blocks(wo, 4).reshape(-1), ffn]
-    if wv is not None:
-        blocks += [proj_stage_blocks(wv, 4).reshape(-1), proj_stage_blocks(wp, 6).reshape(-1)]
-    out = torch.cat(blocks, 0).to(torch.bfloat16).contiguous().view(torch.int16).reshape(-1)
-    need = int(lib().msm_encoder_block_lp_stream_bytes(d_ffn, 0 if wp is None else wp.shape[0]))
-    if out.numel() * 2 != need:
-        raise RuntimeError(f"pack_encoder_block_lp: built {out.numel() * 2} bytes, the kernel expects {need}")
-    return out
-
-
-def encoder_block_lp(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
-                     value_heads=0, eps=1e-5):
-    """encoder_block in the low-precision mode on the K = 32 kernel (wstream from pack_encoder_block_lp); fp32 in, fp32 out."""
-    _c(attn, "attn"), _c(src, "src"), _c(wstream, "wstream", torch.int16), _c(small, "small"), _c(pos, "pos")
-    B, S, C = src.shape
-    src_out = torch.empty_like(src)
-    value_out = proj_out = None
-    if want_next:
-        value_out = torch.empty((B, value_heads, S, C // value_heads), device=src.device, dtype=torch.float32) \
-            if value_heads else torch.empty_like(src)
-        proj_out = torch.empty((B, S, proj_width), device=src.device, dtype=torch.float32)
-    rc = lib().msm_encoder_block_lp_fwd(_p(attn), _p(src), _p(wstream), _p(small), _p(pos), _p(src_out), _p(value_out), _p(proj_out),
-                                        B * S, tokens_per_image or S, d_ffn, proj_width, int(value_heads), eps, _stream())
-    check(rc, "msm_encoder_block_lp_fwd")
-    return src_out, value_out, proj_out
-
-
-# ---- the bf16 plan's encoder layers with head-major bf16 activations (csrc/enc_lp.hip) ------------------------------------
-def _korder_L(K, device):
-    """k order "L" of a K-wide contraction whose B operand comes from layout-L registers (lane (token, lq) holds features
-    fb*16 + lq*4 + r): 32-wide group G, lane quarter kq, element j  <->  column (2G + (j >> 2))*16 + 4 kq + (j & 3)."""
-    G = torch.arange(K // 32, device=device).view(-1, 1, 1)
-    kq = torch.arange(4, device=device).view(1, -1, 1)
-    j = torch.arange(8, device=device).view(1, 1, -1)
-    return (2 * G + (j >> 2)) * 16 + 4 * kq + (j & 3)
-
-
-def _korder_natural(K, device):
-    G = torch.arange(K // 32, device=device).view(-1, 1, 1)
-    kq = torch.arange(4, device=device).view(1, -1, 1)
-    j = torch.arange(8, device=device).view(1, 1, -1)
-    return 32 * G + 8 * kq + j
-
-
-def _frag_blocks(w, korder):
-    """w (R, K) -> (R/16, K/32, 512): 1-KiB A-operand blocks of v_mfma_f32_16x16x32_bf16, block[rb][G][kq*16 + i][j] =
-    w[rb*16 + i][korder[G][kq][j]]."""
-    R, K = w.shape
-    t = w.reshape(R // 16, 16, K)[:, :, korder]              # (rb, i, G, kq, j)
-    return t.permute(0, 2, 3, 1, 4).reshape(R // 16, K // 32, 512)
-
-
-def _hl(w):
-    h = w.to(torch.bfloat16).float()
-    return h, (w - h).to(torch.bfloat16).float()
-
-
-def _value_row_perm(device):
-    """Row (16 rb + 4 lq + r) of the packed value_proj = value feature head*8 + dim with head = 4 (rb >> 1) + lq,
-    dim = 4 (rb & 1) + r: a lane's row blocks 2j, 2j + 1 are the eight dims of one head (one 16-byte store)."""
-    rb = torch.arange(4, device=device).view(-1, 1, 1)
-    lq = torch.arange(4, device=device).view(1, -1, 1)
-    r = torch.arange(4, device=device).view(1, 1, -1)
-    return ((4 * (rb >> 1) + lq) * 8 + 4 * (rb & 1) + r).reshape(-1)
-
-
-def _proj_row_perm(heads, LP, device):
-    """Packed row order of the [sampling_offsets | attention_weights] projection of the bf16 plan: the offsets of all heads (row
-    24 head + c), then the logits (192 + 12 head + c) -- the reference's own row order (ms_deform_attn.py:47-48, 99-101), so a
-    16-row block of the MFMA output is all offsets or all logits (csrc/enc_lp.hip, store_proj_rb).  (Round 4 interleaved them per head.)"""
-    return torch.arange(heads * 3 * LP, device=device)
-
-
-def _proj_row_perm_per_head(heads, LP, device):
-    """Row m*36 + c of the per-head projection blocks of msm_msdeform_attn_enc_lp_fused_fwd = reference row m*2LP + c (offsets,
-    c < 2LP) or heads*2LP + m*LP + c - 2LP (logits)."""
-    m = torch.arange(heads, device=device).view(-1, 1)
-    c = torch.arange(3 * LP, device=device).view(1, -1)
-    return torch.where(c < 2 * LP, m * 2 * LP + c, heads * 2 * LP + m * LP + c - 2 * LP).reshape(-1)
-
-
-PROJ_REC_FLOATS = 30     # the bf16 plan's sampling projection: 120 bytes per (image, head, token) = 24 fp32 offsets + 12 fp16 logits, plane-major
-                         # per (image, head) (csrc/enc_lp.hip, EH_REC); tensors are typed (B, 8, S, 30) float32 for their size only
-
-
-def pack_encoder_block_hm(wo, w1, w2, wv=None, wp=None, ffn_f16=False):
-    """One encoder layer's matrices as the weight stream of msm_encoder_block_hm_fwd (include/msm_hip.h): resident block
-    [output_proj | next layer's value_proj] as [h, l] bf16 pairs, linear1 / linear2 as single bf16 copies -- ``ffn_f16``: as IEEE
-    halves (precision "f16") --, four pairs of 16-wide hidden blocks per 32-KiB stage, then (wv / wp given) the next layer's
-    sampling projection in (head, 36) row order as [h, l] pairs, eight row blocks per stage.  Returns an int16 tensor (bit patterns)."""
-    dev = wo.device
-    d_ffn = w1.shape[0]
-    if wo.shape != (64, 64) or w1.shape[1] != 64 or tuple(w2.shape) != (64, d_ffn) or d_ffn % 32:
-        raise RuntimeError("pack_encoder_block_hm: d_model 64, d_ffn a multiple of 32")
-    if (wv is None) != (wp is None) or (wp is not None and tuple(wp.shape) != (288, 64)):
-        raise RuntimeError("pack_encoder_block_hm: wv and wp (288, 64) go together")
-    pad = (-d_ffn) % 128
-
-    def pair_hl(w, korder):                                   # (R, 64) -> (R/16, 2, 2, 512): [rb][G][h, l]
-        h, l = _hl(w)
-        return torch.stack([_frag_blocks(h, korder), _frag_blocks(l, korder)], 2)
-
-    kL, kn = _korder_L(64, dev), _korder_natural(64, dev)
-    res = [pair_hl(wo, kn).reshape(-1)]
-    res.append(pair_hl(wv[_value_row_perm(dev)], kL).reshape(-1) if wv is not None else torch.zeros(16 * 512, device=dev))
-    w1p = torch.cat([w1, torch.zeros(pad, 64, device=dev)], 0)
-    w2p = torch.cat([w2, torch.zeros(64, pad, device=dev)], 1)
-    npair = (d_ffn + pad) // 32
-    b1 = _frag_blocks(w1p, kL).reshape(npair, 4 * 512)                        # [P][q][G][512]
-    b2 = _frag_blocks(w2p, _korder_L(d_ffn + pad, dev)).permute(1, 0, 2).reshape(npair, 4 * 512)     # [P][ob][512]
-    bits = lambda t, dt: t.to(dt).contiguous().view(torch.int16)             # fp32 -> 16-bit patterns (round to nearest even)
-    parts = [bits(torch.cat(res), torch.bfloat16), bits(torch.cat([b1, b2], 1).reshape(-1), torch.float16 if ffn_f16 else torch.bfloat16)]
-    if wp is not None:
-        pj = pair_hl(wp[_proj_row_perm(8, 12, dev)], kL).reshape(-1)         # 18 row blocks x 4 KiB
-        parts.append(bits(torch.cat([pj, torch.zeros(3 * 16384 - pj.numel(), device=dev)]), torch.bfloat16))
-    out = torch.cat(parts).contiguous()
-    assert out.numel() * 2 == lib().msm_encoder_block_hm_stream_bytes(d_ffn, int(wp is not None))
-    return out
-
-
-def pack_encoder_prologue_hm(wv, wp, bv, bp):
-    """Layer 0's value_proj (64, 64) and [sampling_offsets | attention_weights] (288, 64) as the weight blocks and bias vector of
-    msm_encoder_prologue_hm_fwd: the blocks of pack_encoder_block_hm, value first.  Returns (int16 blocks, float32 small)."""
-    dev = wv.device
-    if tuple(wv.shape) != (64, 64) or tuple(wp.shape) != (288, 64):
-        raise RuntimeError("pack_encoder_prologue_hm: value_proj (64, 64) and a (288, 64) sampling projection")
-    kL = _korder_L(64, dev)
-
-    def pair_hl(w):                                           # (R, 64) -> [rb][G][h, l][512]
-        h, l = _hl(w)
-        return torch.stack([_frag_blocks(h, kL), _frag_blocks(l, kL)], 2).reshape(-1)
-
-    blocks = torch.cat([pair_hl(wv[_value_row_perm(dev)]), pair_hl(wp[_proj_row_perm(8, 12, dev)])]).to(torch.bfloat16).contiguous().view(torch.int16)
-    assert blocks.numel() * 2 == lib().msm_encoder_prologue_hm_weight_bytes()
-    small = torch.cat([bv[_value_row_perm(dev)], bp[_proj_row_perm(8, 12, dev)]]).contiguous()
-    return blocks, small
-
-
-def encoder_prologue_hm(raw, stats, gn_params, level_starts, blocks, small, pos, *, groups=32, eps=1e-5):
-    """encoder_prologue for the bf16 plan with its projections on the bf16 matrix pipe (msm_encoder_prologue_hm_fwd): normalises raw
-    IN PLACE (-> src), returns (src, value (B,8,S,8) fp16, proj (B,8,S,36) fp16).  blocks / small: pack_encoder_prologue_hm."""
-    _c(raw, "raw"), _c(stats, "stats", torch.float64), _c(gn_params, "gn_params"), _c(blocks, "blocks", torch.int16), _c(small, "small"), _c(pos, "pos")
-    B, S, C = raw.shape
-    L = len(level_starts) - 1
-    if C != 64 or tuple(stats.shape) != (L, B, 64, 2) or tuple(gn_params.shape) != (L, 2, 64) or tuple(pos.shape) != (S, 64) or small.numel() != 352:
-        raise RuntimeError("encoder_prologue_hm: inconsistent shapes")
-    value = torch.empty((B, 8, S, 8), device=raw.device, dtype=torch.float16)
-    proj = torch.empty((B, 8, S, PROJ_REC_FLOATS), device=raw.device, dtype=torch.float32)
-    ls = (ctypes.c_int32 * (L + 1))(*[int(v) for v in level_starts])
-    rc = lib().msm_encoder_prologue_hm_fwd(_p(raw), _p(stats), _p(gn_params), ctypes.cast(ls, ctypes.c_void_p), L, int(groups), float(eps),
-                                           _p(blocks), _p(small), _p(pos), _p(raw), _p(value), _p(proj), B, S, _stream())
-    check(rc, "msm_encoder_prologue_hm_fwd")
-    return raw, value, proj
-
-
-def pack_encoder_block_hm_small(bo, g1, be1, b1, b2, g2, be2, bv=None, bp=None):
-    """The fp32 parameter vector of msm_encoder_block_hm_fwd (value_proj / projection biases in the packed row orders, linear1
-    bias zero padded to whole stages)."""
-    dev = bo.device
-    d_ffn = b1.numel()
-    bvp = bv[_value_row_perm(dev)] if bv is not None else torch.zeros(64, device=dev)
-    bpp = bp[_proj_row_perm(8, 12, dev)] if bp is not None else torch.zeros(288, device=dev)
-    out = torch.cat([bo, g1, be1, b2, g2, be2, bvp, bpp, b1, torch.zeros((-d_ffn) % 128, device=dev)]).contiguous()
-    assert out.numel() == lib().msm_encoder_block_hm_small_floats(d_ffn)
-    return out
-
-
-def pack_msda_proj_lp(wp, bp, heads=8, n_levels=3, n_points=4):
-    """[sampling_offsets ; attention_weights] weight (heads*L*P*3, 64) and bias -> the per-head [h, l] bf16 fragment stream
-    (int16, 12 KiB per head) and bias table (heads, 48) of msm_msdeform_attn_enc_lp_fused_fwd."""
-    LP = n_levels * n_points
-    if tuple(wp.shape) != (heads * LP * 3, 64) or bp.numel() != wp.shape[0] or LP != 12:
-        raise RuntimeError("pack_msda_proj_lp: the shipped geometry only (3 levels x 4 points)")
-    dev = wp.device
-    perm = _proj_row_perm_per_head(heads, LP, dev)
-    rows = torch.zeros(heads, 48, 64, device=dev)
-    bias = torch.zeros(heads, 48, device=dev)
-    rows[:, :3 * LP] = wp[perm].reshape(heads, 3 * LP, 64)
-    bias[:, :3 * LP] = bp[perm].reshape(heads, 3 * LP)
-    kL = _korder_L(64, dev)
-    h, l = _hl(rows.reshape(heads * 48, 64))
-    blocks = torch.stack([_frag_blocks(h, kL), _frag_blocks(l, kL)], 2)       # (heads*3, 2, 2, 512)
-    return blocks.reshape(-1).to(torch.bfloat16).contiguous().view(torch.int16), bias.contiguous()
-
-
-def proj_to_head_major_records(proj, heads=8, LP=12):
-    """(B, S, heads*LP*3) fp32 in the reference's [offsets | logits] column order -> the bf16 plan's sampling projection
-    (B, heads, S, 30) float32-TYPED (120 bytes per token; NOT a (.., S, 30) array): per (image, head) six planes [S][4 floats] of fp32
-    offsets then three planes [S][4 halves] of fp16 logits (csrc/enc_lp.hip, EH_REC).  Torch ops: tests and the unfused front end
-    only; the fused prologue writes this layout itself."""
-    B, S, W = proj.shape
-    off = proj[..., :heads * 2 * LP].reshape(B, S, heads, 2 * LP // 4, 4).permute(0, 2, 3, 1, 4).reshape(B, heads, -1)          # (B, heads, 6 S 4)
-    lg = proj[..., heads * 2 * LP:].reshape(B, S, heads, LP // 4, 4).permute(0, 2, 3, 1, 4).to(torch.float16).reshape(B, heads, -1)
-    return torch.cat([off, lg.contiguous().view(torch.float32)], -1).view(B, heads, S, PROJ_REC_FLOATS).contiguous()
-
-
-def proj_records_to_columns(rec, heads=8, LP=12):
-    """Inverse of proj_to_head_major_records (the logits come back as the fp16 values the planes hold): (B, S, heads*LP*3) fp32."""
-    B, M, S, _ = rec.shape
-    flat = rec.reshape(B, M, S * PROJ_REC_FLOATS)
-    off = flat[..., :S * 2 * LP].reshape(B, M, 2 * LP // 4, S, 4).permute(0, 3, 1, 2, 4).reshape(B, S, M * 2 * LP)
-    lg = flat[..., S * 2 * LP:].contiguous().view(torch.float16).reshape(B, M, LP // 4, S, 4).permute(0, 3, 1, 2, 4).reshape(B, S, M * LP).float()
-    return torch.cat([off, lg], -1).contiguous()
-
-
 _GLUE_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
@@ -1856,6 +1483,98 @@ def to_f16(t):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# fused encoder (msdeformattn.py:122-131); the weight streams come from packing.py
+# ----------------------------------------------------------------------------------------------
+def encoder_prologue(raw, stats, gn_params, level_starts, stream, small, pos, proj_width, *, groups=32, eps=1e-5, value_heads=0,
+                     bf16_hm=False):
+    """raw (B,S,64) concatenated input projections (conv1x1_in), stats (L,B,64,2) float64 their GroupNorm moments,
+    gn_params (L,2,64) = gamma, beta, level_starts: L+1 token offsets (0..S).  Normalises raw IN PLACE (-> src) and
+    returns (src, value, proj) for the first encoder layer: value (B,S,64) or head-major (B,heads,S,64/heads),
+    proj (B,S,proj_width) = [sampling_offsets | attention_weights](src + pos).  bf16_hm (8 heads, proj_width 288): value and
+    proj are the bf16 plan's head-major fp16 tensors (B,8,S,8) and (B,8,S,36) (encoder_block_hm)."""
+    _c(raw, "raw"), _c(stats, "stats", torch.float64), _c(gn_params, "gn_params"), _c(stream, "stream"), _c(small, "small"), _c(pos, "pos")
+    B, S, C = raw.shape
+    L = len(level_starts) - 1
+    if C != 64 or tuple(stats.shape) != (L, B, 64, 2) or tuple(gn_params.shape) != (L, 2, 64) or tuple(pos.shape) != (S, 64):
+        raise RuntimeError("encoder_prologue: inconsistent shapes")
+    if small.numel() != 64 + proj_width:
+        raise RuntimeError("encoder_prologue: small must hold the 64 value_proj biases and the proj_width projection biases")
+    dev = raw.device
+    if bf16_hm:
+        value = torch.empty((B, 8, S, 8), device=dev, dtype=torch.float16)
+        proj = torch.empty((B, 8, S, PROJ_REC_FLOATS), device=dev, dtype=torch.float32)
+    else:
+        value = torch.empty((B, value_heads, S, 64 // value_heads) if value_heads else (B, S, 64), device=dev, dtype=torch.float32)
+        proj = torch.empty((B, S, proj_width), device=dev, dtype=torch.float32) if proj_width else None     # 0: value projection only
+    ls = (ctypes.c_int32 * (L + 1))(*[int(v) for v in level_starts])
+    rc = lib().msm_encoder_prologue_fwd(_p(raw), _p(stats), _p(gn_params), ctypes.cast(ls, ctypes.c_void_p), L, int(groups), float(eps),
+                                        _p(stream), _p(small), _p(pos), _p(raw), _p(value), _p(proj), B, S, int(proj_width),
+                                        int(value_heads), int(bool(bf16_hm)), _stream())
+    check(rc, "msm_encoder_prologue_fwd")
+    return raw, value, proj
+
+
+def _encoder_tail(entry, wdtype, attn, src, wstream, small, d_ffn, proj_width, pos, tokens_per_image, want_next, value_heads, eps,
+                  proj_none_if_empty=False):
+    """The launch the three encoder-tail wrappers share: ``entry`` is the msm_encoder_block*_fwd to call, ``wdtype`` the dtype its
+    wstream has.  proj_none_if_empty: proj_out is None, not a (B, S, 0) tensor, when proj_width == 0."""
+    _c(attn, "attn"), _c(src, "src"), _c(wstream, "wstream", wdtype), _c(small, "small"), _c(pos, "pos")
+    B, S, C = src.shape
+    src_out = torch.empty_like(src)
+    value_out = proj_out = None
+    if want_next:
+        value_out = torch.empty((B, value_heads, S, C // value_heads), device=src.device, dtype=torch.float32) \
+            if value_heads else torch.empty_like(src)
+        if proj_width or not proj_none_if_empty:
+            proj_out = torch.empty((B, S, proj_width), device=src.device, dtype=torch.float32)
+    rc = getattr(lib(), entry)(_p(attn), _p(src), _p(wstream), _p(small), _p(pos), _p(src_out), _p(value_out), _p(proj_out),
+                               B * S, tokens_per_image or S, d_ffn, proj_width, int(value_heads), eps, _stream())
+    check(rc, entry)
+    return src_out, value_out, proj_out
+
+
+def encoder_block(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
+                  value_heads=0, eps=1e-5):
+    """One fused encoder-layer tail.  attn/src (B,S,64).  Returns (src_out, value_out, proj_out) with the
+    last two None when want_next is False.  value_heads = h > 0: value_out is head-major (B,h,S,64/h)."""
+    # proj_width == 0: the next layer's gather computes its own sampling projection (ms_deform_attn_encoder_fused)
+    return _encoder_tail("msm_encoder_block_fwd", torch.float32, attn, src, wstream, small, d_ffn, proj_width, pos, tokens_per_image,
+                         want_next, value_heads, eps, proj_none_if_empty=True)
+
+
+def encoder_block_split(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
+                        value_heads=0, eps=1e-5):
+    """encoder_block in fp32 accuracy on the bf16 matrix pipe (wstream from pack_encoder_block_split): fp32 in, fp32 out."""
+    return _encoder_tail("msm_encoder_block_split_fwd", torch.int16, attn, src, wstream, small, d_ffn, proj_width, pos, tokens_per_image,
+                         want_next, value_heads, eps)
+
+
+def encoder_block_lp(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
+                     value_heads=0, eps=1e-5):
+    """encoder_block in the low-precision mode on the K = 32 kernel (wstream from pack_encoder_block_lp); fp32 in, fp32 out."""
+    return _encoder_tail("msm_encoder_block_lp_fwd", torch.int16, attn, src, wstream, small, d_ffn, proj_width, pos, tokens_per_image,
+                         want_next, value_heads, eps)
+
+
+# ---- the bf16 plan's encoder layers with head-major bf16 activations (csrc/enc_lp.hip) ------------------------------------
+def encoder_prologue_hm(raw, stats, gn_params, level_starts, blocks, small, pos, *, groups=32, eps=1e-5):
+    """encoder_prologue for the bf16 plan with its projections on the bf16 matrix pipe (msm_encoder_prologue_hm_fwd): normalises raw
+    IN PLACE (-> src), returns (src, value (B,8,S,8) fp16, proj (B,8,S,36) fp16).  blocks / small: pack_encoder_prologue_hm."""
+    _c(raw, "raw"), _c(stats, "stats", torch.float64), _c(gn_params, "gn_params"), _c(blocks, "blocks", torch.int16), _c(small, "small"), _c(pos, "pos")
+    B, S, C = raw.shape
+    L = len(level_starts) - 1
+    if C != 64 or tuple(stats.shape) != (L, B, 64, 2) or tuple(gn_params.shape) != (L, 2, 64) or tuple(pos.shape) != (S, 64) or small.numel() != 352:
+        raise RuntimeError("encoder_prologue_hm: inconsistent shapes")
+    value = torch.empty((B, 8, S, 8), device=raw.device, dtype=torch.float16)
+    proj = torch.empty((B, 8, S, PROJ_REC_FLOATS), device=raw.device, dtype=torch.float32)
+    ls = (ctypes.c_int32 * (L + 1))(*[int(v) for v in level_starts])
+    rc = lib().msm_encoder_prologue_hm_fwd(_p(raw), _p(stats), _p(gn_params), ctypes.cast(ls, ctypes.c_void_p), L, int(groups), float(eps),
+                                           _p(blocks), _p(small), _p(pos), _p(raw), _p(value), _p(proj), B, S, _stream())
+    check(rc, "msm_encoder_prologue_hm_fwd")
+    return raw, value, proj
+
+
 def encoder_block_hm(attn_hm, src, wstream, small, d_ffn, *, pos=None, want_next=True, eps=1e-5, ffn_f16=False):
     """One encoder-layer tail of the bf16 plan: attn_hm (B, 8, S, 8) fp16, src (B, S, 64) fp32 -> (src_out fp32, and for the
     NEXT layer value_hm (B, 8, S, 8) fp16 and the sampling records proj_hm (B, 8, S, 30) float32-typed (24 fp32 offsets + 12 fp16
@@ -1904,40 +1623,3 @@ def ms_deform_attn_encoder_lp_fused(value_hm, spatial_shapes, level_start_index,
                                                   _p(bpack), _p(out), B, S, M, D, spatial_shapes.shape[0], int(n_points), _stream())
     check(rc, "msm_msdeform_attn_enc_lp_fused_fwd")
     return out
-
-
-def encoder_block_split(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
-                        value_heads=0, eps=1e-5):
-    """encoder_block in fp32 accuracy on the bf16 matrix pipe (wstream from pack_encoder_block_split): fp32 in, fp32 out."""
-    _c(attn, "attn"), _c(src, "src"), _c(wstream, "wstream", torch.int16), _c(small, "small"), _c(pos, "pos")
-    B, S, C = src.shape
-    src_out = torch.empty_like(src)
-    value_out = proj_out = None
-    if want_next:
-        value_out = torch.empty((B, value_heads, S, C // value_heads), device=src.device, dtype=torch.float32) \
-            if value_heads else torch.empty_like(src)
-        proj_out = torch.empty((B, S, proj_width), device=src.device, dtype=torch.float32)
-    rc = lib().msm_encoder_block_split_fwd(_p(attn), _p(src), _p(wstream), _p(small), _p(pos), _p(src_out), _p(value_out), _p(proj_out),
-                                           B * S, tokens_per_image or S, d_ffn, proj_width, int(value_heads), eps, _stream())
-    check(rc, "msm_encoder_block_split_fwd")
-    return src_out, value_out, proj_out
-
-
-def encoder_block(attn, src, wstream, small, d_ffn, proj_width, *, pos=None, tokens_per_image=None, want_next=True,
-                  value_heads=0, eps=1e-5):
-    """One fused encoder-layer tail.  attn/src (B,S,64).  Returns (src_out, value_out, proj_out) with the
-    last two None when want_next is False.  value_heads = h > 0: value_out is head-major (B,h,S,64/h)."""
-    _c(attn, "attn"), _c(src, "src"), _c(wstream, "wstream"), _c(small, "small"), _c(pos, "pos")
-    B, S, C = src.shape
-    M = B * S
-    src_out = torch.empty_like(src)
-    value_out = proj_out = None
-    if want_next:
-        value_out = torch.empty((B, value_heads, S, C // value_heads), device=src.device, dtype=torch.float32) \
-            if value_heads else torch.empty_like(src)
-        # proj_width == 0: the next layer's gather computes its own sampling projection (ms_deform_attn_encoder_fused)
-        proj_out = torch.empty((B, S, proj_width), device=src.device, dtype=torch.float32) if proj_width else None
-    rc = lib().msm_encoder_block_fwd(_p(attn), _p(src), _p(wstream), _p(small), _p(pos), _p(src_out), _p(value_out),
-                                     _p(proj_out), M, tokens_per_image or S, d_ffn, proj_width, int(value_heads), eps, _stream())
-    check(rc, "msm_encoder_block_fwd")
-    return src_out, value_out, proj_out
