@@ -45,6 +45,8 @@
  *                                   (seg2bmap :15-69, boundary_overlap :71-104)
  *   msm_instance_postprocess     <- F.interpolate + instance_inference,
  *                                   MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:337-343,461-497
+ *   msm_instance_postprocess_resized
+ *                                <- the same with sem_seg_postprocess's resize to the requested output size in between, :351-357
  */
 #ifndef MSM_HIP_H
 #define MSM_HIP_H
@@ -61,7 +63,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 24   /* 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 25   /* 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -89,6 +91,7 @@ enum {
     MSM_OPT_MS_SPLIT_KERNEL,    /* msm_ms_hill_climb_split: 1 = X split inside the iteration kernel (fallback of the pre-split planes) */
     MSM_OPT_CONV3_WIDE,         /* msm_conv3x3_c64_f32 / _bf16: 0 = one 16-pixel block per wave, 16 waves per workgroup; 1 = two blocks, 8 waves (default: bf16 only) */
     MSM_OPT_DEC_TILE32,         /* msm_dec_*_f16: 1 = 32-row tiles (two 16-row MFMA tiles share every weight fragment), 0 = 16-row tiles (default: 32 from 4096 rows) */
+    MSM_OPT_POST_RESIZE_DIRECT, /* msm_instance_postprocess_resized: 1 = every tap loaded from the low-res map (the path of strips whose cropped-image tile exceeds the LDS budget) */
     MSM_OPT_COUNT
 };
 int msm_set_option(int key, int value);
@@ -665,6 +668,23 @@ int msm_instance_postprocess(const float* mask_logits, const int32_t* query_inde
                              const float* class_scores, float* pred_masks, float* mask_score, float* boxes,
                              int B, int Q, int T, int h, int w, int H, int W, int Hs, int Ws,
                              float* workspace, void* stream);
+/* The same post-processing with the masks delivered at a requested output size OH x OW (detectron2's inference contract:
+ * the network saw a resized image, "height" / "width" name the size the caller wants; sem_seg_postprocess,
+ * pretrained_meanshiftformer_model.py:351-357): F.interpolate(mode="bilinear", align_corners=False) applied twice, in one pass
+ * that writes only the binary masks.
+ *   stage 1: C[y][x], y < H, x < W = the bilinear sample of the h x w low-res map on the Hs x Ws padded frame (scales h/Hs, w/Ws:
+ *            what msm_instance_postprocess thresholds), cropped to the H x W image;
+ *   stage 2: R[oy][ox] = the bilinear sample of C on the OH x OW grid (scales H/OH, W/OW; source coordinate clamped at 0, the
+ *            upper tap clamped at H-1 / W-1 of the CROPPED image, not of the frame).  No antialiasing: 2 x 2 taps for a downscale too.
+ * Every C tap is an fp32 value hy*(hx*a + lx*b) + ly*(hx*c + lx*d) and R is that expression over four C taps (the stages are
+ * not folded into composite weights: the threshold at 0 makes the rounding visible).  Then as above on the output grid:
+ * pred_masks [B][T][OH*OW] = (R > 0), mask_score, boxes (extents over OH x OW).
+ *   workspace floats >= msm_instance_postprocess_workspace(B, T, OH, OW) (the output grid's partials; same finishing kernel).
+ * OH == H && OW == W is the identity of stage 2 up to rounding; callers use msm_instance_postprocess for it. */
+int msm_instance_postprocess_resized(const float* mask_logits, const int32_t* query_index,
+                                     const float* class_scores, float* pred_masks, float* mask_score, float* boxes,
+                                     int B, int Q, int T, int h, int w, int H, int W, int Hs, int Ws, int OH, int OW,
+                                     float* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Input projections of the pixel decoder: 1x1 convolution of a backbone feature map to 64 channels, written

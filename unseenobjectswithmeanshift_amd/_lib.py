@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmsm_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msm_hip.h")
 
 _lib = None
-ABI_VERSION = 24     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
+ABI_VERSION = 25     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
 
 c_f = ctypes.c_void_p      # float* (device)
 c_p = ctypes.c_void_p
@@ -161,6 +161,7 @@ _SIGNATURES = {
     "msm_point_loss_bwd": (c_i, [c_p, c_p, c_p, c_f, c_f, c_p, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                  c_i, c_i, c_i, c_fl, c_i, c_p]),
     "msm_instance_postprocess": (c_i, [c_f, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "msm_instance_postprocess_resized": (c_i, [c_f, c_p, c_f, c_f, c_f, c_f] + [c_i] * 11 + [c_f, c_p]),
 }
 
 
@@ -194,7 +195,7 @@ def lib():
 # kernel-selection overrides of include/msm_hip.h (enum order), for tools/ and tests/ only
 OPTIONS = ("MASK_NC", "MASKB_TARGET", "GEMM_TILE", "GEMM_SHALLOW", "ATTN_TARGET", "ATTN_KERNEL", "ATTN_QK_MAX", "ATTN_QKCFG",
            "CONVIN_NT", "POST_GENERIC", "ENC_NO_COOP", "MSDA_GENERIC", "MS_CHUNK", "MS_NO_PERSISTENT", "ATTN_FUSED_KV", "KV_PIPE", "MASK_KERNEL",
-           "MS_SPLIT_KERNEL", "CONV3_WIDE", "DEC_TILE32")
+           "MS_SPLIT_KERNEL", "CONV3_WIDE", "DEC_TILE32", "POST_RESIZE_DIRECT")
 OPT_AUTO = -1
 
 

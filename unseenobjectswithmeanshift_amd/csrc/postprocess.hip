@@ -275,6 +275,165 @@ __global__ __launch_bounds__(256) void inst_upsample4_kernel(const float* __rest
     inst_store_partial(acc, bt, sum, cnt, xmin, ymin, xmax, ymax);
 }
 
+// ---- masks at a requested output size (msm_instance_postprocess_resized): upsample -> crop -> resize -> threshold in one pass ----
+// The reference interpolates twice (PM:337-343, then sem_seg_postprocess PM:354-357) and both results are fp32 tensors; the
+// sign of the second one is the mask.  C (stage 1, the cropped image) and R (stage 2, the output grid) keep that shape here:
+// every C tap is rounded to fp32 before R reads it.  The roundings of the expression are spelt out (three FMAs, no further
+// contraction) so that the two paths below give the same bits whatever the compiler does around them.
+__device__ __forceinline__ float bilerp(float hy, float ly, float hx, float lx, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float t0 = __builtin_fmaf(lx, b, hx * a);
+    const float t1 = __builtin_fmaf(lx, d, hx * c);
+    return __builtin_fmaf(ly, t1, hy * t0);                 // hy * (hx*a + lx*b) + ly * (hx*c + lx*d)
+}
+
+// src_index with both taps held inside the map whatever the float rounding of the coordinate does (in range: the same values)
+__device__ __forceinline__ void src_index_in(int dst, float scale, int in, int& i0, int& i1, float& l1) {
+    src_index(dst, scale, in, i0, i1, l1);
+    i0 = min(i0, in - 1);
+    i1 = min(i1, in - 1);
+}
+
+// C[cy][cx]: the low-res map sampled on the padded frame (what inst_upsample_kernel thresholds)
+__device__ __forceinline__ float c_tap(const float* __restrict__ src, int w, int ya, int yb, float ly, int xa, int xb, float lx) {
+    const float* ra = src + ya * w;
+    const float* rb = src + yb * w;
+    return bilerp(1.f - ly, ly, 1.f - lx, lx, ra[xa], ra[xb], rb[xa], rb[xb]);
+}
+
+// grid (column tiles, 16-output-row strips, B*T), one thread per 4 (OW % 4 == 0) or 1 output columns.  A workgroup's pixels read
+// the C rows [r_lo, r_hi] x columns [c_lo, c_hi] only (both coordinate maps are monotone).  When that tile fits the LDS the
+// launch was given, it is computed ONCE per workgroup -- for an upscale every C value serves (OH/H)*(OW/W) outputs, so stage 1
+// all but vanishes -- and a pixel costs four LDS reads; otherwise (large frames shrunk: a 16-row strip spans 16*H/OH C rows of
+// up to W columns) every pixel evaluates its own four C taps from the low-res map, the same c_tap() on the same operands.
+__global__ __launch_bounds__(256) void inst_resize_kernel(const float* __restrict__ logits, const int32_t* __restrict__ qidx,
+                                                          float* __restrict__ masks, InstAcc* __restrict__ acc, int Q, int T,
+                                                          int h, int w, int H, int W, int Hs, int Ws, int OH, int OW,
+                                                          int lds_floats) {
+    extern __shared__ float ctile[];
+    const int bt = blockIdx.z;
+    const int b = bt / T;
+    const int q = min(max(qidx[bt], 0), Q - 1);          // caller-supplied indices never address outside the logits
+    const float* src = logits + ((int64_t)b * Q + q) * h * w;
+    float* dst = masks + (int64_t)bt * OH * OW;
+    const float sy = (float)h / (float)Hs, sx = (float)w / (float)Ws;     // stage 1: the padded frame
+    const float ry = (float)H / (float)OH, rx = (float)W / (float)OW;     // stage 2: the cropped image -> the output grid
+    const int y0 = blockIdx.y * 16, y1 = min(OH, y0 + 16);
+    const bool vec = (OW % 4) == 0;     // 4 pixels per thread, one 16-byte store
+    const int step = vec ? 4 : 1;
+    const int px0 = blockIdx.x * blockDim.x * step, px1 = min(OW, px0 + (int)blockDim.x * step);   // this workgroup's columns (px0 < OW)
+    int r_lo, r_hi, c_lo, c_hi, t0, t1;
+    float tl;
+    src_index_in(y0, ry, H, r_lo, t1, tl);
+    src_index_in(y1 - 1, ry, H, t0, r_hi, tl);
+    src_index_in(px0, rx, W, c_lo, t1, tl);
+    src_index_in(px1 - 1, rx, W, t0, c_hi, tl);
+    const int nr = r_hi - r_lo + 1, nc = c_hi - c_lo + 1;
+    const bool tiled = (int64_t)nr * nc <= (int64_t)lds_floats;           // uniform over the workgroup
+    if (tiled) {
+        for (int r = 0; r < nr; ++r) {
+            int ya, yb;
+            float ly;
+            src_index_in(r_lo + r, sy, h, ya, yb, ly);
+            for (int c = threadIdx.x; c < nc; c += blockDim.x) {
+                int xa, xb;
+                float lx;
+                src_index_in(c_lo + c, sx, w, xa, xb, lx);
+                ctile[r * nc + c] = c_tap(src, w, ya, yb, ly, xa, xb, lx);
+            }
+        }
+        __syncthreads();
+    }
+    double sum = 0.0;
+    unsigned int cnt = 0;
+    int xmin = 0x7fffffff, ymin = 0x7fffffff, xmax = -1, ymax = -1;
+    const int x0 = px0 + threadIdx.x * step;
+    if (x0 < OW) {
+        // the column taps of this thread's pixels, both levels, are the same for every row of the strip
+        int ca[4], cb[4];
+        float lx2[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) src_index_in(min(x0 + e, OW - 1), rx, W, ca[e], cb[e], lx2[e]);
+        int ta[4], tb[4];              // the same columns inside the tile (held there, like the rows below, whatever happens)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ta[e] = min(max(ca[e] - c_lo, 0), nc - 1);
+            tb[e] = min(max(cb[e] - c_lo, 0), nc - 1);
+        }
+        float fsum = 0.f;              // <= 64 sigmoids in fp32, then into the double total
+        int xhit_min = 0x7fffffff, xhit_max = -1;
+        for (int y = y0; y < y1; ++y) {
+            int ra, rb;
+            float ly2;
+            src_index_in(y, ry, H, ra, rb, ly2);                   // wave-uniform
+            const float hy2 = 1.f - ly2;
+            float o[4];
+            bool any = false;
+            if (tiled) {
+                const int ia = min(max(ra - r_lo, 0), nr - 1) * nc, ib = min(max(rb - r_lo, 0), nr - 1) * nc;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o[e] = 0.f;
+                    if (e < step)
+                        o[e] = bilerp(hy2, ly2, 1.f - lx2[e], lx2[e], ctile[ia + ta[e]], ctile[ia + tb[e]], ctile[ib + ta[e]],
+                                      ctile[ib + tb[e]]);
+                }
+            } else {
+                int ya0, yb0, ya1, yb1;
+                float lya, lyb;
+                src_index_in(ra, sy, h, ya0, yb0, lya);
+                src_index_in(rb, sy, h, ya1, yb1, lyb);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o[e] = 0.f;
+                    if (e < step) {
+                        int xa0, xb0, xa1, xb1;
+                        float lxa, lxb;
+                        src_index_in(ca[e], sx, w, xa0, xb0, lxa);
+                        src_index_in(cb[e], sx, w, xa1, xb1, lxb);
+                        o[e] = bilerp(hy2, ly2, 1.f - lx2[e], lx2[e], c_tap(src, w, ya0, yb0, lya, xa0, xb0, lxa),
+                                      c_tap(src, w, ya0, yb0, lya, xa1, xb1, lxb), c_tap(src, w, ya1, yb1, lyb, xa0, xb0, lxa),
+                                      c_tap(src, w, ya1, yb1, lyb, xa1, xb1, lxb));
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float m = o[e];
+                o[e] = 0.f;
+                if (e < step && m > 0.f) {
+                    o[e] = 1.f;
+                    // sigmoid through v_exp_f32 / v_rcp_f32 (relative error ~1e-6; the score is a mean over the mask)
+                    fsum += __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * m));
+                    cnt += 1;
+                    xhit_min = min(xhit_min, x0 + e);
+                    xhit_max = max(xhit_max, x0 + e);
+                    any = true;
+                }
+            }
+            if (any) {
+                ymin = min(ymin, y);
+                ymax = max(ymax, y);
+            }
+            if (vec) *reinterpret_cast<float4*>(dst + (int64_t)y * OW + x0) = make_float4(o[0], o[1], o[2], o[3]);
+            else dst[(int64_t)y * OW + x0] = o[0];
+        }
+        sum = (double)fsum;
+        xmin = xhit_min;
+        xmax = xhit_max;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sum += __shfl_xor(sum, o, 64);
+        cnt += __shfl_xor(cnt, o, 64);
+        xmin = min(xmin, __shfl_xor(xmin, o, 64));
+        ymin = min(ymin, __shfl_xor(ymin, o, 64));
+        xmax = max(xmax, __shfl_xor(xmax, o, 64));
+        ymax = max(ymax, __shfl_xor(ymax, o, 64));
+    }
+    inst_store_partial(acc, bt, sum, cnt, xmin, ymin, xmax, ymax);
+}
+
 __global__ void inst_finish_kernel(const InstAcc* __restrict__ acc, int parts, const float* __restrict__ class_scores,
                                    float* __restrict__ score, float* __restrict__ boxes, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -361,5 +520,39 @@ extern "C" int msm_instance_postprocess(const float* mask_logits, const int32_t*
     hipLaunchKernelGGL(inst_finish_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, acc, (int)(grid.x * grid.y), class_scores, mask_score, boxes,
                        n);
     MSM_CHECK_LAUNCH("msm_instance_postprocess");
+    return MSM_OK;
+}
+
+// floats of LDS a workgroup of the resizing kernel may ask for (48 KB: three workgroups per CU keep the stores flowing)
+static const int kResizeLdsFloats = 12288;
+
+extern "C" int msm_instance_postprocess_resized(const float* mask_logits, const int32_t* query_index,
+                                                const float* class_scores, float* pred_masks,
+                                                float* mask_score, float* boxes, int B, int Q, int T, int h, int w, int H, int W,
+                                                int Hs, int Ws, int OH, int OW, float* workspace, void* stream) {
+    MSM_REQUIRE(mask_logits && query_index && pred_masks && mask_score && boxes && workspace,
+                "msm_instance_postprocess_resized: null pointer");
+    MSM_REQUIRE(B > 0 && Q > 0 && T > 0 && h > 0 && w > 0 && H > 0 && W > 0, "msm_instance_postprocess_resized: bad sizes");
+    MSM_REQUIRE(OH > 0 && OW > 0, "msm_instance_postprocess_resized: bad output size %dx%d", OH, OW);
+    MSM_REQUIRE(Hs >= H && Ws >= W, "msm_instance_postprocess_resized: frame %dx%d smaller than the image %dx%d", Hs, Ws, H, W);
+    MSM_REQUIRE((((uintptr_t)workspace) & 7) == 0 && (((uintptr_t)boxes) & 15) == 0 && (((uintptr_t)pred_masks) & 15) == 0,
+                "msm_instance_postprocess_resized: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    InstAcc* acc = reinterpret_cast<InstAcc*>(workspace);
+    const int n = B * T;
+    const int cols = (OW % 4 == 0) ? OW / 4 : OW;              // the grid of msm_instance_postprocess on the output size: the same workspace
+    const int threads = min(256, cdiv(cols, 64) * 64);
+    dim3 grid(cdiv(cols, threads), cdiv(OH, 16), n);
+    // upper bound of the C tile of a workgroup: k outputs span (k - 1) * scale source positions, + 2 taps, + 1 for the rounding of the
+    // coordinates (the kernel measures its own tile and takes the direct path if this bound should ever be short)
+    const int prow = min(16, OH), pcol = min(threads * ((OW % 4 == 0) ? 4 : 1), OW);
+    const int64_t nr = min((int64_t)H, (int64_t)((double)(prow - 1) * H / OH) + 4);
+    const int64_t nc = min((int64_t)W, (int64_t)((double)(pcol - 1) * W / OW) + 4);
+    const int lds = (nr * nc <= kResizeLdsFloats && opt(MSM_OPT_POST_RESIZE_DIRECT) != 1) ? (int)(nr * nc) : 0;
+    hipLaunchKernelGGL(inst_resize_kernel, grid, dim3(threads), sizeof(float) * lds, st, mask_logits, query_index, pred_masks, acc, Q, T,
+                       h, w, H, W, Hs, Ws, OH, OW, lds);
+    hipLaunchKernelGGL(inst_finish_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, acc, (int)(grid.x * grid.y), class_scores, mask_score, boxes,
+                       n);
+    MSM_CHECK_LAUNCH("msm_instance_postprocess_resized");
     return MSM_OK;
 }

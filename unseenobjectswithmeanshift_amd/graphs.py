@@ -74,10 +74,18 @@ class StaleCheck:
         return (plan_epoch(), len(ts), sum([t._version for t in ts]), sum([t.data_ptr() for t in ts]), self._manual)
 
 
+def _output_key(image_size, output_size):
+    """The requested output size as part of a graph's key: None for the image size itself (the same launches as no request)."""
+    if output_size is None or tuple(output_size) == tuple(image_size):
+        return None
+    return tuple(int(v) for v in output_size)
+
+
 class GraphedInference:
     """``GraphedInference(model)(features, image_size)`` == ``model.inference(features, image_size)`` (meta_arch.py),
     replayed from a HIP graph.  ``features``: dict of device tensors.  The returned tensors are owned by the graph and
-    are overwritten by the next call with the same geometry: ``.clone()`` what must outlive it."""
+    are overwritten by the next call with the same geometry: ``.clone()`` what must outlive it.  ``output_size`` (see
+    ``MeanShiftMaskFormer.inference``) is part of the geometry: one graph per requested output size."""
 
     def __init__(self, model, warmup=2, strict=False, entry="inference"):
         self.model = model
@@ -91,16 +99,17 @@ class GraphedInference:
         """Force a re-capture on the next call (after replacing Parameter objects by hand; see StaleCheck)."""
         self._sig.invalidate()
 
-    def _key(self, features, image_size, padded_size):
+    def _key(self, features, image_size, padded_size, output_size=None):
         return (tuple((k, tuple(v.shape), v.dtype, v.device) for k, v in sorted(features.items())), tuple(image_size),
-                tuple(padded_size or image_size))
+                tuple(padded_size or image_size), _output_key(image_size, output_size))
 
     @torch.no_grad()
-    def __call__(self, features, image_size, padded_size=None):
+    def __call__(self, features, image_size, padded_size=None, output_size=None):
         for v in features.values():
             if not v.is_cuda:
                 raise RuntimeError("GraphedInference needs device tensors (there is no CPU path)")
-        key = self._key(features, image_size, padded_size)
+        key = self._key(features, image_size, padded_size, output_size)
+        kw = {} if key[-1] is None else {"output_size": key[-1]}       # two output sizes are two graphs
         sig = self._sig()
         entry = self._graphs.get(key)
         if entry is not None and entry[3] != sig:          # parameters changed since the capture
@@ -114,11 +123,11 @@ class GraphedInference:
             with torch.cuda.stream(self._stream):
                 run = getattr(self.model, self.entry)
                 for _ in range(self.warmup):                       # builds every weight cache outside the capture
-                    run(static_in, image_size, padded_size)
+                    run(static_in, image_size, padded_size, **kw)
                 self._stream.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, stream=self._stream):
-                    static_out = run(static_in, image_size, padded_size)
+                    static_out = run(static_in, image_size, padded_size, **kw)
             cur.wait_stream(self._stream)
             entry = (graph, static_in, static_out, sig, cache_refs(self.model))
             self._graphs[key] = entry
@@ -183,11 +192,11 @@ class PipelinedInference:
         self._next = 0
 
     @staticmethod
-    def _key(features, image_size, padded_size):
+    def _key(features, image_size, padded_size, output_size=None):
         return (tuple((k, tuple(v.shape), v.dtype, v.device) for k, v in sorted(features.items())), tuple(image_size),
-                tuple(padded_size or image_size))
+                tuple(padded_size or image_size), _output_key(image_size, output_size))
 
-    def _build(self, i, features, image_size, padded_size):
+    def _build(self, i, features, image_size, padded_size, output_size=None):
         old = self._slots[i]
         stream = old[1] if old is not None else _slot_stream(next(iter(features.values())).device, i)
         cur = torch.cuda.current_stream()
@@ -195,13 +204,15 @@ class PipelinedInference:
         with torch.cuda.stream(stream):
             static_in = {k: v.clone() for k, v in features.items()}
             run = getattr(self.model, self.entry)
+            key = self._key(features, image_size, padded_size, output_size)
+            kw = {} if key[-1] is None else {"output_size": key[-1]}
             for _ in range(self.warmup):                           # builds every weight cache outside the capture
-                run(static_in, image_size, padded_size)
+                run(static_in, image_size, padded_size, **kw)
             stream.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
-                static_out = run(static_in, image_size, padded_size)
-        self._slots[i] = (self._key(features, image_size, padded_size), stream, graph, static_in, static_out,
+                static_out = run(static_in, image_size, padded_size, **kw)
+        self._slots[i] = (key, stream, graph, static_in, static_out,
                           torch.cuda.Event(), self._sig(), cache_refs(self.model))
         return self._slots[i]
 
@@ -216,8 +227,9 @@ class PipelinedInference:
         return self._slots[slot][3]
 
     @torch.no_grad()
-    def submit(self, features, image_size, padded_size=None, slot_inputs=False):
-        """Queue one batch; returns the slot handle for ``result``.  Slots are taken round-robin."""
+    def submit(self, features, image_size, padded_size=None, slot_inputs=False, output_size=None):
+        """Queue one batch; returns the slot handle for ``result``.  Slots are taken round-robin.  ``output_size``: as
+        ``MeanShiftMaskFormer.inference``; a slot whose graph was captured for another output size is re-captured."""
         i = self._next
         entry = self._slots[i]
         if slot_inputs:
@@ -227,8 +239,8 @@ class PipelinedInference:
             for v in features.values():
                 if not v.is_cuda:
                     raise RuntimeError("PipelinedInference needs device tensors (there is no CPU path)")
-            if entry is None or entry[0] != self._key(features, image_size, padded_size) or entry[6] != self._sig():
-                entry = self._build(i, features, image_size, padded_size)
+            if entry is None or entry[0] != self._key(features, image_size, padded_size, output_size) or entry[6] != self._sig():
+                entry = self._build(i, features, image_size, padded_size, output_size)
         self._next = (i + 1) % self.depth
         stream, graph, static_in, done = entry[1], entry[2], entry[3], entry[5]
         stream.wait_stream(torch.cuda.current_stream())            # the producer of the inputs runs on the caller's stream

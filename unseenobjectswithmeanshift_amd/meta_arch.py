@@ -75,6 +75,33 @@ class Instances:
         return Instances(self.image_size, **{k: v.to(device) for k, v in self._fields.items()})
 
 
+def group_by_size(sizes):
+    """sizes: one hashable key per sample (here ((H, W), (OH, OW)): image size and requested output size).  Returns (groups,
+    inverse): ``groups`` = [(key, [sample indices, ascending])] in order of first appearance -- one post-processing call each --
+    and ``inverse[i]`` = the position of sample i in the concatenation of the groups' index lists, so that results gathered
+    group by group go back to input order as ``[flat[j] for j in inverse]``."""
+    index = {}
+    groups = []
+    for i, key in enumerate(sizes):
+        if key not in index:
+            index[key] = len(groups)
+            groups.append((key, []))
+        groups[index[key]][1].append(i)
+    inverse = [0] * len(sizes)
+    pos = 0
+    for _, members in groups:
+        for i in members:
+            inverse[i] = pos
+            pos += 1
+    return groups, inverse
+
+
+def _pad_to(x, frame):
+    """Zeros at the right / bottom up to ``frame`` (ImageList.from_tensors)."""
+    dh, dw = frame[0] - x.shape[-2], frame[1] - x.shape[-1]
+    return F.pad(x, (0, dw, 0, dh)) if dh or dw else x
+
+
 class MeanShiftMaskFormerHead(PlanAttributes, nn.Module):
     _version = 2
 
@@ -188,13 +215,9 @@ class MeanShiftMaskFormer(PlanAttributes, nn.Module):
         self.size_divisibility = size_divisibility
         self.instance_on = instance_on
 
-    @torch.no_grad()
-    def inference(self, features, image_size, padded_size=None):
-        """features: dict res2..res5 (B,C,h,w) on the GPU.  Returns the per-batch tensors
-        (scores (B,T), classes (B,T), masks (B,T,H,W), boxes (B,T,4), query_index (B,T)).  ``padded_size``: the frame
-        the features were computed on when the image was padded to the size divisibility (masks are cropped back to
-        image_size, PM:275,354-357)."""
-        padded_size = tuple(padded_size or image_size)
+    def _select(self, features, padded_size):
+        """Head + top-k on a batch of one frame: (low-res mask logits, index of every kept instance into them (B,T) int32, class
+        scores, classes, query_index) -- everything ``inference`` needs before the masks are brought to an image."""
         # the final mask step only for the queries kept below (an argument, not module state: two pipelines may share one model)
         k = int(self.test_topk_per_image) if getattr(self, "topk_before_masks", True) else 0
         if k and _accepts(self.sem_seg_head.forward, "final_topk"):
@@ -211,21 +234,82 @@ class MeanShiftMaskFormer(PlanAttributes, nn.Module):
         else:
             cls_scores, classes, qidx = ops.topk_class_scores(outputs["pred_logits"], self.test_topk_per_image)
             local = qidx
-        # scores = class prob * mean mask prob (PM:495), fused into the post-process kernel
-        masks, scores, boxes = ops.instance_postprocess(outputs["pred_masks"], local, image_size, class_scores=cls_scores,
-                                                        padded_size=padded_size)
-        return scores, classes, masks, boxes, qidx
+        return outputs["pred_masks"], local, cls_scores, classes, qidx
 
     @torch.no_grad()
-    def inference_images(self, inputs, image_size, padded_size=None):
+    def inference(self, features, image_size, padded_size=None, output_size=None):
+        """features: dict res2..res5 (B,C,h,w) on the GPU.  Returns the per-batch tensors
+        (scores (B,T), classes (B,T), masks (B,T,H,W), boxes (B,T,4), query_index (B,T)).  ``padded_size``: the frame
+        the features were computed on when the image was padded to the size divisibility (masks are cropped back to
+        image_size, PM:275,354-357).  ``output_size`` (OH, OW): the size the caller wants the instances at when the network
+        saw a resized image (sem_seg_postprocess's second interpolation, PM:354-357): masks (B,T,OH,OW), scores and boxes on
+        that grid; None = image_size."""
+        padded_size = tuple(padded_size or image_size)
+        low, local, cls_scores, classes, qidx = self._select(features, padded_size)
+        # scores = class prob * mean mask prob (PM:495), fused into the post-process kernel
+        masks, scores, boxes = ops.instance_postprocess(low, local, image_size, class_scores=cls_scores,
+                                                        padded_size=padded_size, output_size=output_size)
+        return scores, classes, masks, boxes, qidx
+
+    def _image_features(self, inputs):
+        return self.backbone(inputs["image"], inputs["depth"]) if "depth" in inputs else self.backbone(inputs["image"])
+
+    @torch.no_grad()
+    def inference_images(self, inputs, image_size, padded_size=None, output_size=None):
         """``inference`` with the backbone in front: inputs {"image": (B,3,Hp,Wp)[, "depth": (B,3,Hp,Wp)]} already padded to the
         size divisibility (and normalised, if this meta-arch normalises).  One call = the whole model; ``graphed(entry=
         "inference_images")`` replays it from a HIP graph (MIOpen's convolutions capture like any other launch once their
         algorithms have been chosen by the warm-up passes)."""
         if self.backbone is None:
             raise RuntimeError("inference_images needs a backbone")
-        feats = self.backbone(inputs["image"], inputs["depth"]) if "depth" in inputs else self.backbone(inputs["image"])
-        return self.inference(feats, image_size, padded_size)
+        return self.inference(self._image_features(inputs), image_size, padded_size, output_size)
+
+    def _forward_images(self, batched_inputs, keys, normalise):
+        """The image path of ``forward`` (both meta-archs).  ``keys``: the sample fields that are images ("image"[, "depth"]);
+        ``normalise``: applied to each of them before the padding.
+        One dict holding 4-D batches means one size for all; a list of samples may mix image sizes: every image is padded at
+        the right / bottom to the common frame (the maximum height and width, rounded up to the size divisibility:
+        ImageList.from_tensors, PM:275), the network runs once and the instances are post-processed per group of samples
+        that share (image size, output size), PM:348-357.  "height" / "width" of a sample name the output size (default: its
+        image's size)."""
+        first = batched_inputs[0]
+        div = max(int(self.size_divisibility), 1)
+        if first[keys[0]].dim() == 4:
+            batch = {k: first[k] for k in keys}
+            n = batch[keys[0]].shape[0]
+            H, W = (int(v) for v in batch[keys[0]].shape[-2:])
+            sizes = [((H, W), (int(first.get("height", H)), int(first.get("width", W))))] * n
+            samples = None
+        else:
+            samples = batched_inputs
+            sizes = []
+            for x in samples:
+                H, W = (int(v) for v in x[keys[0]].shape[-2:])
+                sizes.append(((H, W), (int(x.get("height", H)), int(x.get("width", W)))))
+        frame = (-(-max(s[0][0] for s in sizes) // div) * div, -(-max(s[0][1] for s in sizes) // div) * div)
+        if samples is not None and len(set(s[0] for s in sizes)) > 1:
+            # normalise each image BEFORE it is padded: the border is zero in normalised space
+            batch = {k: torch.stack([_pad_to(normalise(x[k]), frame) for x in samples]) for k in keys}
+        else:
+            if samples is not None:
+                batch = {k: torch.stack([x[k] for x in samples]) for k in keys}
+            batch = {k: _pad_to(normalise(v), frame) for k, v in batch.items()}
+        groups, inverse = group_by_size(sizes)
+        if len(groups) == 1:
+            (image_size, output_size), _ = groups[0]
+            scores, classes, masks, boxes, _ = self.inference_images(batch, image_size, frame, output_size)
+            flat = [(output_size, masks[b], boxes[b], scores[b], classes[b]) for b in range(scores.shape[0])]
+        else:
+            low, local, cls_scores, classes, _ = self._select(self._image_features(batch), frame)
+            flat = []
+            for (image_size, output_size), members in groups:
+                idx = torch.tensor(members, device=low.device)
+                masks, scores, boxes = ops.instance_postprocess(low.index_select(0, idx), local.index_select(0, idx), image_size,
+                                                                class_scores=cls_scores.index_select(0, idx), padded_size=frame,
+                                                                output_size=output_size)
+                flat += [(output_size, masks[j], boxes[j], scores[j], classes[i]) for j, i in enumerate(members)]
+        return [{"instances": Instances(o, pred_masks=m, pred_boxes=bx, scores=sc, pred_classes=cl)}
+                for o, m, bx, sc, cl in (flat[j] for j in inverse)]
 
     def set_precision(self, mode):
         """See MeanShiftMaskFormerHead.set_precision; a backbone with a ``backbone_dtype`` switch (ResNet50Backbone) follows."""
@@ -253,10 +337,12 @@ class MeanShiftMaskFormer(PlanAttributes, nn.Module):
     @torch.no_grad()
     def forward(self, batched_inputs):
         """batched_inputs: list of dicts with "image" (3,H,W) -- or one dict holding a 4-D batch, as
-        the reference accepts (PM:270-273) -- plus, when ``backbone`` is None, "features"."""
+        the reference accepts (PM:270-273) -- plus, when ``backbone`` is None, "features".  With images, "height" / "width" of
+        a sample name the size its instances are returned at (the detectron2 contract for inputs resized before the network:
+        ``_forward_images``); with "features" they name the image inside the padded frame and there is no output resize."""
         first = batched_inputs[0]
         div = self.size_divisibility
-        if self.backbone is None:
+        if self.backbone is None and "features" in first:
             feats = first["features"] if isinstance(first["features"], dict) and first["features"]["res2"].dim() == 4 \
                 else {k: torch.stack([x["features"][k] for x in batched_inputs]) for k in first["features"]}
             padded = (4 * feats["res2"].shape[-2], 4 * feats["res2"].shape[-1])       # the frame the features cover
@@ -266,16 +352,10 @@ class MeanShiftMaskFormer(PlanAttributes, nn.Module):
             if not (padded[0] - div < H <= padded[0] and padded[1] - div < W <= padded[1]):
                 raise ValueError(f"height/width {H}x{W} do not fit features of a {padded[0]}x{padded[1]} frame")
         else:
-            images = first["image"] if first["image"].dim() == 4 else torch.stack([x["image"] for x in batched_inputs])
-            H, W = images.shape[-2:]
-            if first.get("height", H) != H or first.get("width", W) != W:
-                raise NotImplementedError("output height/width other than the image size (sem_seg_postprocess resize, PM:354)")
-            padded = (-(-H // div) * div, -(-W // div) * div)
-            if self.pixel_mean is not None:                                   # meanshiftformer_model.py:241, before the padding
-                images = (images - self.pixel_mean) / self.pixel_std
-            if padded != (H, W):            # ImageList.from_tensors(images, size_divisibility): zeros at the right / bottom
-                images = F.pad(images, (0, padded[1] - W, 0, padded[0] - H))
-            feats = self.backbone(images)
+            if self.backbone is None:
+                raise RuntimeError("forward needs a backbone or samples with \"features\"")
+            mean, std = self.pixel_mean, self.pixel_std                       # meanshiftformer_model.py:241, before the padding
+            return self._forward_images(batched_inputs, ("image",), (lambda v: v) if mean is None else (lambda v: (v - mean) / std))
         scores, classes, masks, boxes, _ = self.inference(feats, (int(H), int(W)), padded)
         results = []
         for b in range(scores.shape[0]):
@@ -296,41 +376,23 @@ class PretrainedMeanShiftMaskFormer(MeanShiftMaskFormer):
 
     @torch.no_grad()
     def forward(self, batched_inputs):
-        first = batched_inputs[0]
-        images = first["image"] if first["image"].dim() == 4 else torch.stack([x["image"] for x in batched_inputs])
-        depth = None
-        if self.use_depth:
-            depth = first["depth"] if first["depth"].dim() == 4 else torch.stack([x["depth"] for x in batched_inputs])
-        H, W = int(images.shape[-2]), int(images.shape[-1])
-        if first.get("height", H) != H or first.get("width", W) != W:
-            raise NotImplementedError("output height/width other than the image size (sem_seg_postprocess resize, PM:354)")
-        div = max(int(self.size_divisibility), 1)
-        padded = (-(-H // div) * div, -(-W // div) * div)
-        if padded != (H, W):                      # ImageList.from_tensors: zeros at the right / bottom (PM:275, 286)
-            images = F.pad(images, (0, padded[1] - W, 0, padded[0] - H))
-            depth = None if depth is None else F.pad(depth, (0, padded[1] - W, 0, padded[0] - H))
-        scores, classes, masks, boxes, _ = self.inference_images({"image": images, **({} if depth is None else {"depth": depth})}, (H, W), padded)
-        return [{"instances": Instances((H, W), pred_masks=masks[b], pred_boxes=boxes[b], scores=scores[b], pred_classes=classes[b])}
-                for b in range(scores.shape[0])]
+        """See MeanShiftMaskFormer._forward_images; "depth" follows "image" (same size, same padding, PM:275, 286); no normalisation."""
+        return self._forward_images(batched_inputs, ("image", "depth") if self.use_depth else ("image",), lambda v: v)
 
-    def inference_images(self, inputs, image_size, padded_size=None):
-        """The whole RGB-D model on padded inputs {"image": (B,3,Hp,Wp)[, "depth": xyz (B,3,Hp,Wp)]}: the two towers (SEG.py:88-117,
-        ``backbone(img, label=None, depth)``), the channel normalisation of pretrained_meanshiftformer_model.py:298-300, the head
-        and the post-processing; ``graphed(entry="inference_images")`` / ``pipelined`` replay exactly this."""
-        if self.backbone is None:
-            raise RuntimeError("inference_images needs a backbone")
+    def _image_features(self, inputs):
+        """The RGB-D front of ``inference_images`` on padded inputs {"image": (B,3,Hp,Wp)[, "depth": xyz (B,3,Hp,Wp)]}: the two towers
+        (SEG.py:88-117, ``backbone(img, label=None, depth)``) and the channel normalisation of pretrained_meanshiftformer_model.py:
+        298-300; the head and the post-processing follow in ``inference``, and ``graphed(entry="inference_images")`` / ``pipelined``
+        replay exactly that chain."""
         depth = inputs.get("depth") if self.use_depth else None
         if _accepts(self.backbone.forward, "renormalize"):
             # PM:298-300 (F.normalize over channels) inside the backbone's fused tail: no further pass over the embedding
-            feats = {"res5": self.backbone(inputs["image"], None, depth, renormalize=True).float().contiguous()}
-            return self.inference(feats, image_size, padded_size)
+            return {"res5": self.backbone(inputs["image"], None, depth, renormalize=True).float().contiguous()}
         feats = self.backbone(inputs["image"], None, depth)
         feats = feats.float().contiguous()
         if feats.is_cuda:
-            feats = {"res5": ops.l2_normalize_nchw(feats)}                                # PM:298-300 (F.normalize over channels)
-        else:
-            feats = {"res5": F.normalize(feats, p=2, dim=1).contiguous()}
-        return self.inference(feats, image_size, padded_size)
+            return {"res5": ops.l2_normalize_nchw(feats)}                                # PM:298-300 (F.normalize over channels)
+        return {"res5": F.normalize(feats, p=2, dim=1).contiguous()}
 
 
 def build_ucn_model(num_queries=100, dec_layers=6, use_depth=True, **head_kw):

@@ -1216,24 +1216,35 @@ def topk_class_scores(pred_logits, topk, gather=None, gather_cols=None):
     return scores, classes, qidx, sel
 
 
-def instance_postprocess(mask_logits, query_index, image_size, class_scores=None, padded_size=None):
+def instance_postprocess(mask_logits, query_index, image_size, class_scores=None, padded_size=None, output_size=None):
     """mask_logits (B,Q,h,w), query_index int32 (B,T) -> (pred_masks (B,T,H,W) float 0/1,
     score (B,T) = mean mask probability [* class_scores], boxes (B,T,4)).  The logits are upsampled to ``padded_size``
     (the frame the network saw, default = image_size) and cropped to image_size = (H, W), as the reference does for
-    inputs padded to the size divisibility (PM:337-343 + sem_seg_postprocess, PM:354-357)."""
+    inputs padded to the size divisibility (PM:337-343 + sem_seg_postprocess, PM:354-357).  ``output_size`` (OH, OW) other than
+    image_size: the cropped logits are interpolated a second time to that size (sem_seg_postprocess's resize, the "height" /
+    "width" of a sample whose image was resized for the network) and masks (B,T,OH,OW), scores and boxes are taken there, in
+    one pass (msm_instance_postprocess_resized)."""
     _c(mask_logits, "mask_logits"), _c(query_index, "query_index", torch.int32), _c(class_scores, "class_scores")
     B, Q, h, w = mask_logits.shape
     T = query_index.shape[1]
     H, W = int(image_size[0]), int(image_size[1])
     Hs, Ws = (H, W) if padded_size is None else (int(padded_size[0]), int(padded_size[1]))
+    OH, OW = (H, W) if output_size is None else (int(output_size[0]), int(output_size[1]))
+    if OH <= 0 or OW <= 0:
+        raise RuntimeError(f"instance_postprocess: output_size {OH}x{OW} must be positive")
     dev = mask_logits.device
-    masks = torch.empty((B, T, H, W), device=dev, dtype=torch.float32)
+    masks = torch.empty((B, T, OH, OW), device=dev, dtype=torch.float32)
     score = torch.empty((B, T), device=dev, dtype=torch.float32)
     boxes = torch.empty((B, T, 4), device=dev, dtype=torch.float32)
-    ws = torch.empty((int(lib().msm_instance_postprocess_workspace(B, T, H, W)),), device=dev, dtype=torch.float32)
-    rc = lib().msm_instance_postprocess(_p(mask_logits), _p(query_index), _p(class_scores), _p(masks), _p(score), _p(boxes),
-                                        B, Q, T, h, w, H, W, Hs, Ws, _p(ws), _stream())
-    check(rc, "msm_instance_postprocess")
+    ws = torch.empty((int(lib().msm_instance_postprocess_workspace(B, T, OH, OW)),), device=dev, dtype=torch.float32)
+    if (OH, OW) == (H, W):
+        rc = lib().msm_instance_postprocess(_p(mask_logits), _p(query_index), _p(class_scores), _p(masks), _p(score), _p(boxes),
+                                            B, Q, T, h, w, H, W, Hs, Ws, _p(ws), _stream())
+        check(rc, "msm_instance_postprocess")
+    else:
+        rc = lib().msm_instance_postprocess_resized(_p(mask_logits), _p(query_index), _p(class_scores), _p(masks), _p(score),
+                                                    _p(boxes), B, Q, T, h, w, H, W, Hs, Ws, OH, OW, _p(ws), _stream())
+        check(rc, "msm_instance_postprocess_resized")
     return masks, score, boxes
 
 
