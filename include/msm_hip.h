@@ -47,6 +47,8 @@
  *                                   MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:337-343,461-497
  *   msm_instance_postprocess_resized
  *                                <- the same with sem_seg_postprocess's resize to the requested output size in between, :351-357
+ *   msm_ingest_frames            <- read_sample tools/test_image_with_ms_transformer.py:115-147, run_network
+ *                                   ros/test_images_segmentation_transformer.py:159-173, compute_xyz lib/fcn/get_backbone.py:96-102
  */
 #ifndef MSM_HIP_H
 #define MSM_HIP_H
@@ -63,7 +65,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 25   /* 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 26   /* 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -925,6 +927,30 @@ int msm_crop_resize(const float* rgb, const float* depth, const float* labels, c
                     float* depth_out, float* mask_out, int N, int H, int W, int S, void* stream);
 int msm_paste_labels(const float* renum, const int32_t* table, const int32_t* order, const int32_t* frame_start,
                      float* refined, int F, int H, int W, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Camera frames: a batch of raw frames -> the two NCHW fp32 tensors the network sees, in ONE launch (the reference builds them
+ * on the host, one frame at a time: read_sample tools/test_image_with_ms_transformer.py:115-147, run_network
+ * ros/test_images_segmentation_transformer.py:159-173, compute_xyz lib/fcn/get_backbone.py:96-102).
+ *   color      [F][H][W][3] uint8, channel order as given by swap_rb
+ *   depth      [F][H][W] uint16 (depth_is_u16) or float32; NULL: no xyz output (xyz_out NULL too)
+ *   depth_div  uint16 only: z = float(d) / depth_div (1000.0f for millimetres)
+ *   lut        [3][256] float: the image value per OUTPUT channel and byte value; the host builds it as
+ *              float32(v) / float32(255) - float32(mean[c] / 255.0), so the image is bit exact by construction
+ *   cam        [F][4] float (device): fx, fy, px, py, one row per frame; may be NULL without depth
+ *   image_out  [F][3][Hp][Wp], xyz_out [F][3][Hp][Wp] or NULL; Hp >= H, Wp >= W (the frame padded to the size divisibility)
+ * Every step is fp32, round to nearest, in this order (no multiply-add, no reciprocal):
+ *   image[c][y][x] = lut[c][color[y][x][c']]           c' = c, or 2 - c when swap_rb is set
+ *   z              = float(d) / depth_div              float32 depth: z = d, NaN -> 0
+ *   xyz[0]         = ((float(x) - px) * z) / fx
+ *   xyz[1]         = ((float(y) - py) * z) / fy
+ *   xyz[2]         = z
+ * Rows y >= H and columns x >= W of the frame are written as 0 in both tensors by the same launch.  Four pixels of a row per lane
+ * with 16-byte stores where W % 4 == 0 (loads) / Wp % 4 == 0 (stores) and the pointers are aligned, element-wise otherwise:
+ * the same values either way.  F Hp ceil(Wp / 4) < 2^31.  `stream` is a hipStream_t. */
+int msm_ingest_frames(const uint8_t* color, const void* depth, int depth_is_u16, float depth_div, const float* lut,
+                      const float* cam, float* image_out, float* xyz_out, int F, int H, int W, int Hp, int Wp, int swap_rb,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Segmentation metrics: every integer count of multilabel_metrics (lib/utils/evaluation.py:109-258) for B pairs of label

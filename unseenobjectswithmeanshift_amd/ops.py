@@ -1433,6 +1433,49 @@ def paste_labels(renum, table, order, frame_start, frames, H, W):
     return refined
 
 
+_DEPTH_U16 = (torch.uint16, torch.int16)          # int16 holding the same bits (torch builds without uint16 kernels)
+
+
+def ingest_frames(color, depth, cam, lut, *, depth_div=1000.0, swap_rb=False, frame=None, out_image=None, out_depth=None):
+    """Raw camera frames -> the network's input tensors in one launch (msm_ingest_frames): color (F,H,W,3) uint8, depth (F,H,W)
+    uint16 / int16 bits (z = d / depth_div) or float32 (metres, NaN -> 0) or None, cam (F,4) float fx, fy, px, py, lut (3,256)
+    float (frames.image_lut) -> (image (F,3,Hp,Wp), xyz (F,3,Hp,Wp) or None), zero outside the H x W image.  ``frame`` = (Hp, Wp)
+    (default (H, W)); ``out_image`` / ``out_depth`` are written in place when given (e.g. the static input buffers of a graph slot)."""
+    _c(color, "color", torch.uint8), _c(cam, "cam"), _c(lut, "lut")
+    if color.dim() != 4 or color.shape[-1] != 3:
+        raise RuntimeError(f"ingest_frames: color {tuple(color.shape)} must be (F, H, W, 3)")
+    F_, H, W, _ = color.shape
+    Hp, Wp = (H, W) if frame is None else (int(frame[0]), int(frame[1]))
+    dev = color.device
+    if tuple(lut.shape) != (3, 256):
+        raise RuntimeError(f"ingest_frames: lut {tuple(lut.shape)} must be (3, 256)")
+    is_u16 = 0
+    if depth is not None:
+        if depth.dtype not in _DEPTH_U16 + (torch.float32,):
+            raise RuntimeError(f"ingest_frames: depth must be uint16 (or int16 bits) or float32, got {depth.dtype}")
+        _c(depth, "depth", depth.dtype)
+        is_u16 = 1 if depth.dtype in _DEPTH_U16 else 0
+        if tuple(depth.shape) != (F_, H, W):
+            raise RuntimeError(f"ingest_frames: depth {tuple(depth.shape)} must be {(F_, H, W)}")
+        if cam is None or tuple(cam.shape) != (F_, 4):
+            raise RuntimeError(f"ingest_frames: cam must be ({F_}, 4) fx, fy, px, py")
+    elif out_depth is not None:
+        raise RuntimeError("ingest_frames: out_depth without depth")
+    outs = []
+    for t, name, want in ((out_image, "out_image", True), (out_depth, "out_depth", depth is not None)):
+        if t is None:
+            t = torch.empty((F_, 3, Hp, Wp), device=dev, dtype=torch.float32) if want else None
+        else:
+            _c(t, name)
+            if tuple(t.shape) != (F_, 3, Hp, Wp) or t.device != dev:
+                raise RuntimeError(f"ingest_frames: {name} {tuple(t.shape)} on {t.device} must be {(F_, 3, Hp, Wp)} on {dev}")
+        outs.append(t)
+    image, xyz = outs
+    check(lib().msm_ingest_frames(_p(color), _p(depth), is_u16, float(depth_div), _p(lut), _p(cam), _p(image), _p(xyz), F_, H, W, Hp, Wp,
+                                  1 if swap_rb else 0, _stream()), "msm_ingest_frames")
+    return image, xyz
+
+
 # ----------------------------------------------------------------------------------------------
 # backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------

@@ -364,6 +364,42 @@ def test_dataset_crop(dataset, predictor, predictor_crop, **kw):
 # (ops.paste_labels).  Two device -> host transfers per batch in all (the label statistics that define the ROIs, the
 # depth keys that order the paste).  Per frame the results are those of test_sample_crop_nolabel (non-NMS form).
 # ----------------------------------------------------------------------------------------------------------------------
+def _raw_batch(samples):
+    """True when the samples hold raw camera frames ("color" (H,W,3) uint8, "depth_raw" (H,W) uint16 or float32, "camera_params" --
+    frames.ingest's arguments) instead of the finished float tensors ("image_color", "depth"); a batch holds one kind."""
+    raw = ["color" in s for s in samples]
+    if any(raw) and not all(raw):
+        raise ValueError("raw camera frames (\"color\") and float samples (\"image_color\") cannot be mixed in one batch")
+    return bool(raw) and raw[0]
+
+
+def _raw_tensor(a):
+    """A raw colour / depth image as a tensor where it lives (numpy -> host tensor); uint16 as int16 holding the same bits (what
+    ops.ingest_frames and frames.ingest take: torch has few uint16 kernels)."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def _raw_arrays(samples, key, dtypes, shape=None):
+    """samples[f][key] of a raw batch as tensors (_raw_tensor), checked to be ONE kind: one of ``dtypes``, one shape (``shape`` when
+    given), all on the host or all on one device -- a ValueError names the first sample that differs."""
+    arrays = [_raw_tensor(s[key]) for s in samples]
+    first = arrays[0]
+    if first.dtype not in dtypes:
+        raise ValueError(f"raw frames: \"{key}\" must be one of {[str(d) for d in dtypes]} (uint16 as such or as int16 bits), got {first.dtype}")
+    want = tuple(first.shape) if shape is None else tuple(shape)
+    for f, t in enumerate(arrays):
+        if tuple(t.shape) != want:
+            raise ValueError(f"raw frames: \"{key}\" of sample {f} has shape {tuple(t.shape)}, {want} expected")
+        if t.dtype != first.dtype or t.device != first.device:
+            raise ValueError(f"raw frames: \"{key}\" of sample {f} is {t.dtype} on {t.device}, sample 0 is {first.dtype} on {first.device}: "
+                             "one dtype and one place per batch")
+    return arrays
+
+
+_RAW_COLOR, _RAW_DEPTH = (torch.uint8,), (torch.int16, torch.float32)
+
+
 def _batch_tensors(predictor, samples):
     """(scores (B,K), classes (B,K), masks (B,K,H,W)) of a list of samples: a predictor that exposes ``batch_tensors`` hands the
     batched tensors of its model over as they are; otherwise the per-sample Instances are stacked (a copy)."""
@@ -508,25 +544,34 @@ def match_label_crop_batched(initial_masks, labels_crop, out_label_crop, rows, d
 
 
 def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7,
-                            low_threshold=0.4, num_class=2, depth_threshold=0.5, crop_batch=256, stages=None):
+                            low_threshold=0.4, num_class=2, depth_threshold=0.5, crop_batch=256, stages=None, order="bgr",
+                            depth_scale=1000.0):
     """test_sample_crop_nolabel (non-NMS form) for a list of frames of one size, batched end to end.
-    samples: [{"image_color" (3,H,W), "depth" (3,H,W), ...}, ...] on the GPU.  Returns (out_label (F,H,W), refined (F,H,W) or
+    samples: [{"image_color" (3,H,W), "depth" (3,H,W), ...}, ...] on the GPU -- or raw camera frames [{"color" (H,W,3) uint8,
+    "depth_raw" (H,W) uint16 (/ ``depth_scale``) or float32 metres, "camera_params"}, ...] in channel order ``order``, all of one
+    dtype and in one place, ingested in one launch (frames.ingest).  Returns (out_label (F,H,W), refined (F,H,W) or
     None, rows) -- frame f's results equal test_sample_crop_nolabel(samples[f], ...)[0][0] / [1][0]; ``rows`` is the ROI table
     (frame, label, x0, y0, x1, y1, 0, 0) of the second stage.  ``stages``: a dict that receives the intermediate tensors
     (crops, second-stage label images) -- for tests."""
     return _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk, confident_score=confident_score,
                        low_threshold=low_threshold, num_class=num_class, depth_threshold=depth_threshold, crop_batch=crop_batch,
-                       stages=stages)[1:]
+                       stages=stages, order=order, depth_scale=depth_scale)[1:]
 
 
 def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confident_score, low_threshold, num_class, depth_threshold,
-                crop_batch, stages):
+                crop_batch, stages, order="bgr", depth_scale=1000.0):
     """test_batch_crop_nolabel's steps -> (first-stage label images before the depth filter, out_label, refined, rows)."""
-    images = torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples]).float().contiguous()
+    if _raw_batch(samples):                                  # camera frames: the whole batch ingested at once (one launch on the device)
+        from . import frames
+        color = torch.stack(_raw_arrays(samples, "color", _RAW_COLOR))
+        images, depths = frames.ingest(color, torch.stack(_raw_arrays(samples, "depth_raw", _RAW_DEPTH, color.shape[1:3])) if use_depth else None,
+                                       [s["camera_params"] for s in samples] if use_depth else None, order=order, depth_scale=depth_scale)
+    else:
+        images = torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples]).float().contiguous()
+        depths = None
+        if use_depth:
+            depths = torch.stack([s["depth"][0] if s["depth"].dim() == 4 else s["depth"] for s in samples]).float().contiguous()
     Fr, _, H, W = images.shape
-    depths = None
-    if use_depth:
-        depths = torch.stack([s["depth"][0] if s["depth"].dim() == 4 else s["depth"] for s in samples]).float().contiguous()
     first = [{"image": images[f], "depth": depths[f] if depths is not None else None, "height": H, "width": W} for f in range(Fr)]
     kw = dict(topk=topk, confident_score=confident_score, low_threshold=low_threshold, num_class=num_class)
     scores, classes, masks = _batch_tensors(predictor, first)
@@ -558,15 +603,16 @@ def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confiden
 
 
 def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4,
-                    num_class=2, depth_threshold=0.5, crop_batch=256):
-    """The labelled form of test_batch_crop_nolabel: every frame of the batch scored against its sample's ground truth
+                    num_class=2, depth_threshold=0.5, crop_batch=256, order="bgr", depth_scale=1000.0):
+    """The labelled form of test_batch_crop_nolabel (raw camera frames included): every frame of the batch scored against its sample's ground truth
     ("label", else "labels") -> (metrics, metrics_refined), two lists of per-frame dicts equal to test_sample_crop(samples[f],
     ...): the first-stage label image before the depth filter, and the refined image of a frame that has crops, else its
     depth-filtered first-stage image.  All 2F images are scored by ONE evaluation.multilabel_metrics_batched call."""
     from .evaluation import multilabel_metrics_batched
     label, out_label, refined, rows = _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk,
                                                   confident_score=confident_score, low_threshold=low_threshold, num_class=num_class,
-                                                  depth_threshold=depth_threshold, crop_batch=crop_batch, stages=None)
+                                                  depth_threshold=depth_threshold, crop_batch=crop_batch, stages=None, order=order,
+                                                  depth_scale=depth_scale)
     Fr = label.shape[0]
     dev = label.device
     gt = torch.stack([_sample_gt(s).to(dev).float() for s in samples])
@@ -596,7 +642,10 @@ class BatchedTwoStage:
       host      paste order from the keys; renumbering + paste-back launches (eager: their shapes depend on N)
 
     ``run(batches)`` keeps TWO batches in flight (two slots, one stream each): while the host waits for one slot's statistics
-    or keys, the GPU works on the other slot.  ``__call__(samples)`` runs one batch on slot 0.  Per frame the results are those
+    or keys, the GPU works on the other slot.  ``__call__(samples)`` runs one batch on slot 0.  A batch of raw camera frames
+    (samples with "color" / "depth_raw" / "camera_params", see test_batch_crop_nolabel; channel order ``order`` and uint16 depth unit
+    ``depth_scale`` are the pipeline's) is uploaded as it is and turned into the slot's input tensors by one eager launch in front
+    of graph 1 (_ingest_raw).  Per frame the results are those
     of test_batch_crop_nolabel up to the batch-size dependence of the head's reduction orders (a padded second-stage batch is a
     different batch size: tests hold the pipeline to the same oracle bounds as the eager form).
 
@@ -604,8 +653,11 @@ class BatchedTwoStage:
     (graphs.StaleCheck)."""
 
     def __init__(self, model, frames, size, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4, num_class=2,
-                 depth_threshold=0.5, bucket=16, crop_size=CROP_SIZE, slots=2, graphs=True):
+                 depth_threshold=0.5, bucket=16, crop_size=CROP_SIZE, slots=2, graphs=True, order="bgr", depth_scale=1000.0):
         from .graphs import StaleCheck, _slot_stream
+        if order not in ("bgr", "rgb"):
+            raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+        self.order, self.depth_scale = order, float(depth_scale)
         self.model = model
         self.frames, (self.H, self.W) = int(frames), (int(size[0]), int(size[1]))
         self.use_depth = bool(use_depth)
@@ -673,20 +725,60 @@ class BatchedTwoStage:
         st["refs"].append(cache_refs(self.model))              # the derived tensors the graph reads by address stay alive with it
         return g, out
 
+    def _ingest_raw(self, st, samples):
+        """A batch of raw camera frames into the slot's static inputs (on the slot's stream): host frames go through the slot's pinned
+        staging buffers and ONE asynchronous copy per array, 5 bytes per pixel instead of the 24 of the float tensors; then one
+        eager launch of the ingest kernel writes st["images"] / st["depths"] -- the buffers the graphs read, so the graphs and their
+        capture are as they were.  The staging buffers are allocated on the first raw batch (a float-only user never pays for them)."""
+        from . import frames, ops
+        Fr, H, W, dev = self.frames, self.H, self.W, self.dev
+        cols = _raw_arrays(samples, "color", _RAW_COLOR, (H, W, 3))              # the frame size the pipeline was built for
+        deps = _raw_arrays(samples, "depth_raw", _RAW_DEPTH, (H, W)) if st["depths"] is not None else None
+        ddt = deps[0].dtype if deps else None
+        r = st.get("raw")
+        if r is None or r["ddt"] != ddt:
+            r = dict(ddt=ddt, ev=torch.cuda.Event(), lut=frames._device_lut(dev, frames.PIXEL_MEANS),
+                     color=torch.empty((Fr, H, W, 3), dtype=torch.uint8, device=dev),
+                     color_host=torch.empty((Fr, H, W, 3), dtype=torch.uint8).pin_memory(), depth=None, depth_host=None, cam=None, cam_host=None)
+            if ddt is not None:
+                r.update(depth=torch.empty((Fr, H, W), dtype=ddt, device=dev), depth_host=torch.empty((Fr, H, W), dtype=ddt).pin_memory(),
+                         cam=torch.empty((Fr, 4), device=dev), cam_host=torch.empty((Fr, 4)).pin_memory())
+            st["raw"] = r
+        r["ev"].synchronize()                                  # the previous batch's copies out of the pinned buffers are done
+        for name, arrays in (("color", cols), ("depth", deps)):
+            if arrays is None:
+                continue
+            if arrays[0].is_cuda:                              # frames that are on the device already: no staging
+                torch.stack(arrays, out=r[name])
+            else:
+                torch.stack(arrays, out=r[name + "_host"])
+                r[name].copy_(r[name + "_host"], non_blocking=True)
+        if deps is not None:
+            r["cam_host"].copy_(frames.camera_table([s["camera_params"] for s in samples], Fr))
+            r["cam"].copy_(r["cam_host"], non_blocking=True)
+        r["ev"].record(st["stream"])
+        ops.ingest_frames(r["color"], r["depth"], r["cam"], r["lut"], depth_div=self.depth_scale, swap_rb=self.order == "rgb",
+                          out_image=st["images"], out_depth=st["depths"])
+
     # ---- the phases of one batch on one slot (all device work on the slot's stream) ----
     @torch.no_grad()
     def _phase1(self, st, samples):
         if len(samples) != self.frames:
             raise ValueError(f"BatchedTwoStage was built for {self.frames} frames, got {len(samples)}")
+        raw = _raw_batch(samples)
         sig = self._sig()
         if st["sig"] != sig:                                   # first use, plan switch or parameter update: re-capture everything
             st["stream"].synchronize()
             st.update(sig=sig, g1=None, g2={}, s2={}, label=None, refs=[])
         with torch.cuda.stream(st["stream"]):
             st["stream"].wait_stream(torch.cuda.current_stream())
-            torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples], out=st["images"])
+            if raw:
+                self._ingest_raw(st, samples)
+            else:
+                torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples], out=st["images"])
             if st["depths"] is not None:
-                torch.stack([s["depth"][0] if s["depth"].dim() == 4 else s["depth"] for s in samples], out=st["depths"])
+                if not raw:
+                    torch.stack([s["depth"][0] if s["depth"].dim() == 4 else s["depth"] for s in samples], out=st["depths"])
                 thr = [0.8 if "OSD" in str(s.get("file_name", "")) else self.depth_threshold for s in samples]      # test_utils.py:384-387
                 if thr != st["thr_host"]:
                     st["thr"].copy_(torch.tensor(thr, dtype=torch.float32)[:, None])
