@@ -47,6 +47,7 @@
  *                                   MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:337-343,461-497
  *   msm_instance_postprocess_resized
  *                                <- the same with sem_seg_postprocess's resize to the requested output size in between, :351-357
+ *   msm_mask_nms                 <- nms lib/fcn/nms.py:3-23 + combine_masks_with_NMS lib/fcn/test_utils.py:55-91, batched
  *   msm_ingest_frames            <- read_sample tools/test_image_with_ms_transformer.py:115-147, run_network
  *                                   ros/test_images_segmentation_transformer.py:159-173, compute_xyz lib/fcn/get_backbone.py:96-102
  */
@@ -65,7 +66,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 26   /* 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 27   /* 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -927,6 +928,35 @@ int msm_crop_resize(const float* rgb, const float* depth, const float* labels, c
                     float* depth_out, float* mask_out, int N, int H, int W, int S, void* stream);
 int msm_paste_labels(const float* renum, const int32_t* table, const int32_t* order, const int32_t* frame_start,
                      float* refined, int F, int H, int W, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mask NMS for B images (nms lib/fcn/nms.py:3-23 + combine_masks_with_NMS lib/fcn/test_utils.py:55-91: the reference's
+ * configuration for real images, USE_NMS test_utils.py:30), fixed shapes, no host synchronisation.
+ *
+ * Inputs per image: masks [K][H][W] (non-zero = inside), scores [K] fp32, candidate [K] uint8 (non-zero = selected by
+ * get_confident_instances; a flag, not a compaction).
+ *   - inter[i][j] = number of pixels inside both masks, area[i] = inter[i][i]: int32, exact.
+ *   - Candidates are visited in descending score order; equal scores the HIGHER index first (a stable ascending argsort,
+ *     reversed).  A NaN score is never a candidate.  A candidate whose mask is empty is dropped before NMS (the reference
+ *     raises on min() of an empty array there; a captured pipeline cannot raise).
+ *   - Greedy suppression: with kept i, candidate j survives iff float32(inter) / float32(area_i + area_j - inter) <= thresh,
+ *     ONE correctly rounded fp32 division (every operand is an integer <= H*W <= 2^24); a NaN quotient suppresses.
+ *   - Kept instances are ordered by area ascending, equal areas in the order they were kept; rank r carries label 2 + r.
+ *   - label[y][x] = the largest label among the kept masks covering the pixel (larger masks overwrite smaller ones), 0
+ *     when none does; score_img[y][x] = trunc(float32(score_k) * float32(100)) of that same mask, 0 when none.
+ *   - bbox[r] = (x_min, y_min, x_max, y_max, score) of the WHOLE kept mask of rank r, fp32; rows from count on are zero.
+ *   - count = number kept; inst_labels[k] = the label instance k carries (0 = not kept).
+ *
+ * masks [B][K][H][W], scores [B][K], candidate [B][K] -> label / score_img [B][H][W] fp32, bbox [B][K][5] fp32, count [B]
+ * int32, inst_labels [B][K] int32.  workspace: msm_mask_nms_workspace(B, K, H, W) bytes, 16-byte aligned; afterwards it
+ * holds the bit planes of the candidate masks (one 64-bit word per 64 consecutive pixels of the flattened image; the planes of
+ * other instances are never written -- nor are their masks read) and inter [B][K][K] over the candidates.
+ * Shapes the kernels do not take -- B, K, H or W <= 0, K > 256, H*W > 2^24, B > 65535 -- return MSM_E_INVALID (the
+ * workspace query too); a workspace that is too small returns MSM_E_WORKSPACE. */
+int64_t msm_mask_nms_workspace(int B, int K, int H, int W);
+int msm_mask_nms(const float* masks, const float* scores, const uint8_t* candidate, float thresh, float* label, float* score_img,
+                 float* bbox, int32_t* count, int32_t* inst_labels, void* workspace, int64_t workspace_bytes, int B, int K, int H,
+                 int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Camera frames: a batch of raw frames -> the two NCHW fp32 tensors the network sees, in ONE launch (the reference builds them

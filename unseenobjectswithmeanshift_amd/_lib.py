@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmsm_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msm_hip.h")
 
 _lib = None
-ABI_VERSION = 26     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
+ABI_VERSION = 27     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
 
 c_f = ctypes.c_void_p      # float* (device)
 c_p = ctypes.c_void_p
@@ -150,6 +150,8 @@ _SIGNATURES = {
     "msm_label_image": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
     "msm_crop_resize": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
     "msm_paste_labels": (c_i, [c_f, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_p]),
+    "msm_mask_nms_workspace": (c_l, [c_i, c_i, c_i, c_i]),
+    "msm_mask_nms": (c_i, [c_f, c_f, c_p, c_fl, c_f, c_f, c_f, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
     "msm_ingest_frames": (c_i, [c_p, c_p, c_i, c_fl, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "msm_instance_postprocess_workspace": (c_l, [c_i, c_i, c_i, c_i]),
     "msm_eval_counts_workspace": (c_l, [c_i]),

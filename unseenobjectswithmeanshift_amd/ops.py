@@ -1408,6 +1408,45 @@ def label_image(masks, inst_labels):
     return out
 
 
+def mask_nms_workspace_bytes(B, K, H, W):
+    """Bytes of workspace msm_mask_nms needs for masks (B,K,H,W) (bit planes + the intersection matrix)."""
+    n = lib().msm_mask_nms_workspace(int(B), int(K), int(H), int(W))
+    if n < 0:
+        check(int(n), "msm_mask_nms_workspace")
+    return int(n)
+
+
+def mask_nms(masks, scores, candidate, thresh=0.7, workspace=None):
+    """Mask NMS of B images in five launches without a host synchronisation (msm_mask_nms; the definition is in
+    include/msm_hip.h and two_stage.combine_masks_with_NMS_batched): masks (B,K,H,W) float32 (non-zero = inside), scores (B,K)
+    float32, candidate (B,K) bool or uint8 -> (label (B,H,W) float32, score (B,H,W) float32, bbox (B,K,5) float32, count (B,)
+    int32, inst_labels (B,K) int32).  ``workspace``: a uint8 tensor of at least mask_nms_workspace_bytes(B,K,H,W) bytes that a
+    caller replaying the launches from a HIP graph owns; allocated here when None."""
+    _c(masks, "masks"), _c(scores, "scores")
+    if candidate is not None and candidate.dtype == torch.bool:
+        candidate = candidate.view(torch.uint8)
+    _c(candidate, "candidate", torch.uint8)
+    if candidate is None:
+        raise RuntimeError("candidate must be a (B,K) bool or uint8 tensor on the GPU")
+    B, K, H, W = masks.shape
+    if tuple(scores.shape) != (B, K) or tuple(candidate.shape) != (B, K):
+        raise RuntimeError(f"scores / candidate must be (B,K) = ({B},{K}), got {tuple(scores.shape)} / {tuple(candidate.shape)}")
+    dev = masks.device
+    need = mask_nms_workspace_bytes(B, K, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _c(workspace, "workspace", torch.uint8)
+    label = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    score_img = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    bbox = torch.empty((B, K, 5), device=dev, dtype=torch.float32)
+    count = torch.empty((B,), device=dev, dtype=torch.int32)
+    inst_labels = torch.empty((B, K), device=dev, dtype=torch.int32)
+    rc = lib().msm_mask_nms(_p(masks), _p(scores), _p(candidate), float(thresh), _p(label), _p(score_img), _p(bbox), _p(count),
+                            _p(inst_labels), _p(workspace), workspace.numel(), B, K, H, W, _stream())
+    check(rc, "msm_mask_nms")
+    return label, score_img, bbox, count, inst_labels
+
+
 def crop_resize(rgb, depth, labels, table, size):
     """ROI crops of a batch of frames in one launch (msm_crop_resize): rgb / depth (F,3,H,W), labels (F,H,W) float, table (N,8)
     int32 rows (frame, label, x0, y0, x1, y1, 0, 0) -> (rgb_crops (N,3,S,S), mask_crops (N,S,S), depth_crops or None)."""

@@ -13,6 +13,7 @@ return values:
   test_sample_crop          <- lib/fcn/test_utils.py:245-336
   test_dataset(_crop)       <- lib/fcn/test_utils.py:424-513   (the printed means, returned)
   test_batch_crop           the labelled form of test_batch_crop_nolabel (one metrics call per batch)
+  combine_masks_with_NMS_batched  nms + combine_masks_with_NMS for a batch of images without compaction or host round trip
 
 These are data-dependent, tiny (<= 20 instances) bookkeeping steps; they run as torch ops on
 whatever device the label maps live on (GPU in production, CPU in the unit tests), never through
@@ -24,7 +25,11 @@ the oracle.  Differences from the reference, on purpose:
   * test_sample / test_sample_crop read the ground truth from sample["label"], else sample["labels"] -- the reference's
     test_sample_crop tests "label" twice (test_utils.py:252-255), so a sample with "labels" only has no ground truth there
     and multilabel_metrics fails on it;
-  * the labelled functions return the metrics (and test_dataset / test_dataset_crop the means) instead of printing them.
+  * the labelled functions return the metrics (and test_dataset / test_dataset_crop the means) instead of printing them;
+  * combine_masks_with_NMS_batched (the batched pipelines with use_nms=True) drops a candidate whose mask is EMPTY before NMS --
+    the reference raises on min() of an empty array there (test_utils.py:85-88), and a pipeline captured in a HIP graph cannot
+    raise; it also fixes what numpy's default argsort leaves open: equal scores are visited higher index first, equal areas are
+    numbered in the order they were kept.
 """
 import numpy as np
 import torch
@@ -362,7 +367,8 @@ def test_dataset_crop(dataset, predictor, predictor_crop, **kw):
 # on all frames in one call, every frame's ROIs are cut in one launch (ops.crop_resize), all crops of all frames go
 # through the second stage in batches of `crop_batch` (measured at 171 crops: one call 20.8 ms, three calls of <= 64 22.2 ms), and every frame's refined labels are pasted in one launch
 # (ops.paste_labels).  Two device -> host transfers per batch in all (the label statistics that define the ROIs, the
-# depth keys that order the paste).  Per frame the results are those of test_sample_crop_nolabel (non-NMS form).
+# depth keys that order the paste).  Per frame the results are those of test_sample_crop_nolabel; with use_nms=True the label
+# images of both stages come from combine_masks_with_NMS_batched (no transfer either).
 # ----------------------------------------------------------------------------------------------------------------------
 def _raw_batch(samples):
     """True when the samples hold raw camera frames ("color" (H,W,3) uint8, "depth_raw" (H,W) uint16 or float32, "camera_params" --
@@ -411,14 +417,91 @@ def _batch_tensors(predictor, samples):
             torch.stack([i.get("pred_masks") for i in inst]))
 
 
+def candidate_flags(scores, classes, topk, confident_score, low_threshold, num_class):
+    """The get_confident_instances selection (test_utils.py:35-52) as a flag per instance instead of a compaction: scores /
+    classes (B,K) -> (B,K) bool.  What instance_labels numbers and combine_masks_with_NMS_batched takes as ``candidate``."""
+    if topk:
+        return ((classes == 1) & (scores > low_threshold)) if num_class >= 2 else torch.ones_like(scores, dtype=torch.bool)
+    return scores > confident_score
+
+
 def instance_labels(scores, classes, topk, confident_score, low_threshold, num_class):
     """The label each instance carries in the label image (label_image above, batched): 2 + (kept instances before it), 0
     when the instance is dropped (get_confident_instances, test_utils.py:35-52).  scores / classes (B,K) -> (B,K) float."""
-    if topk:
-        keep = ((classes == 1) & (scores > low_threshold)) if num_class >= 2 else torch.ones_like(scores, dtype=torch.bool)
-    else:
-        keep = scores > confident_score
+    keep = candidate_flags(scores, classes, topk, confident_score, low_threshold, num_class)
     return ((torch.cumsum(keep, 1) + 1) * keep).float()
+
+
+def _mask_nms_host(masks, scores, candidate, thresh):
+    """combine_masks_with_NMS_batched's definition in numpy integer and fp32 operations (host tensors: the CPU tests)."""
+    m = masks.numpy() != 0
+    s_all = scores.numpy().astype(np.float32)
+    c_all = candidate.numpy() != 0
+    B, K, H, W = m.shape
+    label, score = np.zeros((B, H, W), dtype=np.float32), np.zeros((B, H, W), dtype=np.float32)
+    bbox, count = np.zeros((B, K, 5), dtype=np.float32), np.zeros((B,), dtype=np.int32)
+    thr = np.float32(thresh)
+    for b in range(B):
+        s = s_all[b]
+        idx = np.nonzero(c_all[b] & ~np.isnan(s))[0]
+        flat = m[b, idx].reshape(len(idx), H * W).astype(np.int32)
+        inter = flat @ flat.T                                         # exact int32 counts
+        area = np.diag(inter)
+        pos = np.nonzero(area > 0)[0]                                 # an empty candidate is dropped before NMS
+        order = pos[np.argsort(s[idx[pos]], kind="stable")[::-1]]     # descending score, equal scores the higher index first
+        alive = np.ones(len(order), dtype=bool)
+        keep = []
+        for p, i in enumerate(order):
+            if not alive[p]:
+                continue
+            keep.append(i)
+            rest = order[p + 1:]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                iou = inter[i, rest].astype(np.float32) / (area[i] + area[rest] - inter[i, rest]).astype(np.float32)
+            alive[p + 1:] &= iou <= thr                               # one fp32 division; a NaN quotient suppresses
+        keep = np.array(keep, dtype=np.int64)
+        keep = keep[np.argsort(area[keep], kind="stable")]            # area ascending, equal areas in the order kept
+        for r, i in enumerate(keep):
+            k = idx[i]
+            sel = m[b, k]
+            label[b][sel] = r + 2                                     # larger masks overwrite smaller ones
+            score[b][sel] = np.trunc(np.float32(s[k]) * np.float32(100))
+            ys, xs = np.nonzero(sel)
+            bbox[b, r] = [xs.min(), ys.min(), xs.max(), ys.max(), s[k]]
+        count[b] = len(keep)
+    return torch.from_numpy(label), torch.from_numpy(score), torch.from_numpy(bbox), torch.from_numpy(count)
+
+
+def combine_masks_with_NMS_batched(masks, scores, candidate, thresh=0.7, workspace=None):
+    """nms (lib/fcn/nms.py:3-23) + combine_masks_with_NMS (lib/fcn/test_utils.py:55-91) for B images at once, on fixed shapes:
+    masks (B,K,H,W) (non-zero = inside), scores (B,K), candidate (B,K) bool -- the get_confident_instances selection as a FLAG
+    (candidate_flags), not a compaction -> (label (B,H,W), score (B,H,W), bbox (B,K,5), count (B,) int32), all float32 but count.
+
+    Definition (the same text is in include/msm_hip.h), per image:
+      * inter[i][j] = number of pixels inside both masks, area[i] = inter[i][i]: int32, exact.
+      * Candidates are visited in descending score order; equal scores the higher index first (a stable ascending argsort,
+        reversed).  A NaN score is never a candidate.  A candidate whose mask is empty is dropped before NMS.
+      * Greedy suppression: with kept i, candidate j survives iff float32(inter) / float32(area_i + area_j - inter) <=
+        float32(thresh) -- one correctly rounded fp32 division; a NaN quotient suppresses.
+      * Kept instances are ordered by area ascending, equal areas in the order they were kept; rank r carries label 2 + r.
+      * label[y][x] = the largest label among the kept masks covering the pixel (larger masks overwrite smaller ones), else 0;
+        score[y][x] = trunc(float32(score_k) * float32(100)) of that same mask, else 0.
+      * bbox[r] = (x_min, y_min, x_max, y_max, score) of the WHOLE kept mask of rank r; rows from count on are zero; count =
+        number kept.
+
+    Device tensors go through the HIP kernels (ops.mask_nms: bit planes, popcounts, no host synchronisation; ``workspace`` as
+    there); host tensors -- the CPU tests -- through the same definition in numpy integer and fp32 operations."""
+    B, K, H, W = masks.shape
+    if tuple(scores.shape) != (B, K) or tuple(candidate.shape) != (B, K):
+        raise ValueError(f"scores / candidate must be (B,K) = ({B},{K}), got {tuple(scores.shape)} / {tuple(candidate.shape)}")
+    if B == 0 or K == 0:
+        dev = masks.device
+        return (torch.zeros((B, H, W), device=dev), torch.zeros((B, H, W), device=dev), torch.zeros((B, K, 5), device=dev),
+                torch.zeros((B,), dtype=torch.int32, device=dev))
+    if masks.is_cuda:
+        from . import ops
+        return ops.mask_nms(masks.float().contiguous(), scores.float().contiguous(), (candidate != 0).contiguous(), thresh, workspace)[:4]
+    return _mask_nms_host(masks, scores.float(), candidate, thresh)
 
 
 def roi_table(stats, overflow, H, W):
@@ -545,8 +628,11 @@ def match_label_crop_batched(initial_masks, labels_crop, out_label_crop, rows, d
 
 def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7,
                             low_threshold=0.4, num_class=2, depth_threshold=0.5, crop_batch=256, stages=None, order="bgr",
-                            depth_scale=1000.0):
-    """test_sample_crop_nolabel (non-NMS form) for a list of frames of one size, batched end to end.
+                            depth_scale=1000.0, use_nms=False, nms_thresh=0.7, extras=None):
+    """test_sample_crop_nolabel for a list of frames of one size, batched end to end.  ``use_nms``: both stages build their label
+    images through combine_masks_with_NMS_batched at ``nms_thresh`` (the reference's configuration for real images, test_utils.py:30,
+    376, 396-405) instead of the plain overwrite order, and ``extras`` (a dict) receives the first stage's "out_score" (F,H,W), "bbox"
+    (F,K,5) and "count" (F,).
     samples: [{"image_color" (3,H,W), "depth" (3,H,W), ...}, ...] on the GPU -- or raw camera frames [{"color" (H,W,3) uint8,
     "depth_raw" (H,W) uint16 (/ ``depth_scale``) or float32 metres, "camera_params"}, ...] in channel order ``order``, all of one
     dtype and in one place, ingested in one launch (frames.ingest).  Returns (out_label (F,H,W), refined (F,H,W) or
@@ -555,11 +641,11 @@ def test_batch_crop_nolabel(samples, predictor, predictor_crop=None, *, use_dept
     (crops, second-stage label images) -- for tests."""
     return _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk, confident_score=confident_score,
                        low_threshold=low_threshold, num_class=num_class, depth_threshold=depth_threshold, crop_batch=crop_batch,
-                       stages=stages, order=order, depth_scale=depth_scale)[1:]
+                       stages=stages, order=order, depth_scale=depth_scale, use_nms=use_nms, nms_thresh=nms_thresh, extras=extras)[1:]
 
 
 def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confident_score, low_threshold, num_class, depth_threshold,
-                crop_batch, stages, order="bgr", depth_scale=1000.0):
+                crop_batch, stages, order="bgr", depth_scale=1000.0, use_nms=False, nms_thresh=0.7, extras=None):
     """test_batch_crop_nolabel's steps -> (first-stage label images before the depth filter, out_label, refined, rows)."""
     if _raw_batch(samples):                                  # camera frames: the whole batch ingested at once (one launch on the device)
         from . import frames
@@ -575,7 +661,13 @@ def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confiden
     first = [{"image": images[f], "depth": depths[f] if depths is not None else None, "height": H, "width": W} for f in range(Fr)]
     kw = dict(topk=topk, confident_score=confident_score, low_threshold=low_threshold, num_class=num_class)
     scores, classes, masks = _batch_tensors(predictor, first)
-    label = out_label = _label_image_batched(masks, instance_labels(scores, classes, **kw))
+    if use_nms:
+        label, out_score, bbox, count = combine_masks_with_NMS_batched(masks, scores, candidate_flags(scores, classes, **kw), nms_thresh)
+        out_label = label
+        if extras is not None:
+            extras.update(out_score=out_score, bbox=bbox, count=count)
+    else:
+        label = out_label = _label_image_batched(masks, instance_labels(scores, classes, **kw))
     if depths is not None:
         thr = torch.tensor([0.8 if "OSD" in str(s.get("file_name", "")) else depth_threshold for s in samples],
                            device=images.device, dtype=torch.float32)[:, None]          # test_utils.py:384-387
@@ -595,7 +687,10 @@ def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confiden
         crops = [{"image": rgb_crop[i], "height": CROP_SIZE, "width": CROP_SIZE,
                   "depth": depth_crop[i] if depth_crop is not None else None} for i in range(c0, c1)]
         s2, k2, m2 = _batch_tensors(predictor_crop, crops)
-        labels_crop[c0:c1] = _label_image_batched(m2, instance_labels(s2, k2, **kw))
+        if use_nms:
+            labels_crop[c0:c1] = combine_masks_with_NMS_batched(m2, s2, candidate_flags(s2, k2, **kw), nms_thresh)[0]
+        else:
+            labels_crop[c0:c1] = _label_image_batched(m2, instance_labels(s2, k2, **kw))
     if stages is not None:
         stages.update(rgb_crop=rgb_crop, mask_crop=mask_crop, depth_crop=depth_crop, labels_crop=labels_crop.clone())
     refined = match_label_crop_batched(out_label, labels_crop, mask_crop, rows, depth_crop)
@@ -603,7 +698,7 @@ def _batch_crop(samples, predictor, predictor_crop, *, use_depth, topk, confiden
 
 
 def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4,
-                    num_class=2, depth_threshold=0.5, crop_batch=256, order="bgr", depth_scale=1000.0):
+                    num_class=2, depth_threshold=0.5, crop_batch=256, order="bgr", depth_scale=1000.0, use_nms=False, nms_thresh=0.7):
     """The labelled form of test_batch_crop_nolabel (raw camera frames included): every frame of the batch scored against its sample's ground truth
     ("label", else "labels") -> (metrics, metrics_refined), two lists of per-frame dicts equal to test_sample_crop(samples[f],
     ...): the first-stage label image before the depth filter, and the refined image of a frame that has crops, else its
@@ -612,7 +707,7 @@ def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, 
     label, out_label, refined, rows = _batch_crop(samples, predictor, predictor_crop, use_depth=use_depth, topk=topk,
                                                   confident_score=confident_score, low_threshold=low_threshold, num_class=num_class,
                                                   depth_threshold=depth_threshold, crop_batch=crop_batch, stages=None, order=order,
-                                                  depth_scale=depth_scale)
+                                                  depth_scale=depth_scale, use_nms=use_nms, nms_thresh=nms_thresh)
     Fr = label.shape[0]
     dev = label.device
     gt = torch.stack([_sample_gt(s).to(dev).float() for s in samples])
@@ -630,7 +725,7 @@ def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, 
 # overlapped with the other batch in flight.
 # ----------------------------------------------------------------------------------------------------------------------
 class BatchedTwoStage:
-    """test_batch_crop_nolabel (non-NMS form, lib/fcn/test_utils.py:339-421 per frame) for batches of ``frames`` frames of one
+    """test_batch_crop_nolabel (lib/fcn/test_utils.py:339-421 per frame) for batches of ``frames`` frames of one
     size, with the model called directly (``model.inference_images``: backbone + head + post-processing) and both stages replayed
     from HIP graphs:
 
@@ -649,12 +744,21 @@ class BatchedTwoStage:
     of test_batch_crop_nolabel up to the batch-size dependence of the head's reduction orders (a padded second-stage batch is a
     different batch size: tests hold the pipeline to the same oracle bounds as the eager form).
 
+    ``use_nms=True`` (the reference's configuration for real images, test_utils.py:30): the label images of both stages come from
+    combine_masks_with_NMS_batched at ``nms_thresh`` -- fixed shapes, no host synchronisation, so the launches sit inside both graphs,
+    each with a workspace of its own (one per slot, one per crop bucket).  The first stage's ``out_score`` (F,H,W), ``bbox`` (F,K,5) and
+    ``count`` (F,) are reachable as ``pipeline.extras`` from the moment ``consume`` is called for a batch (tensors owned by the slot,
+    valid until its next batch); ``run`` without a consumer clones them, one dict per batch, into ``pipeline.batch_extras``.
+
     The captured graphs follow the model's execution plan: a plan switch (set_precision, ...) or a parameter update re-captures
     (graphs.StaleCheck)."""
 
     def __init__(self, model, frames, size, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4, num_class=2,
-                 depth_threshold=0.5, bucket=16, crop_size=CROP_SIZE, slots=2, graphs=True, order="bgr", depth_scale=1000.0):
+                 depth_threshold=0.5, bucket=16, crop_size=CROP_SIZE, slots=2, graphs=True, order="bgr", depth_scale=1000.0,
+                 use_nms=False, nms_thresh=0.7):
         from .graphs import StaleCheck, _slot_stream
+        self.use_nms, self.nms_thresh = bool(use_nms), float(nms_thresh)
+        self.extras, self.batch_extras = None, []
         if order not in ("bgr", "rgb"):
             raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
         self.order, self.depth_scale = order, float(depth_scale)
@@ -676,7 +780,7 @@ class BatchedTwoStage:
         Fr, H, W, dev = self.frames, self.H, self.W, self.dev
         k = int(LABEL_BINS)
         with torch.cuda.stream(stream):
-            st = dict(stream=stream, sig=None, g1=None, g2={}, label=None, s2={},
+            st = dict(stream=stream, sig=None, g1=None, g2={}, label=None, s2={}, nms_ws=None, extras=None,
                       images=torch.zeros((Fr, 3, H, W), device=dev), depths=torch.zeros((Fr, 3, H, W), device=dev) if self.use_depth else None,
                       thr=torch.full((Fr, 1), self.depth_threshold, device=dev), thr_host=[self.depth_threshold] * Fr,
                       host_stats=torch.zeros(Fr * k * 5 + Fr, dtype=torch.int32).pin_memory(),
@@ -690,9 +794,21 @@ class BatchedTwoStage:
         sc, cl, mk = self.model.inference_images(inputs, tuple(int(v) for v in images.shape[-2:]))[:3]
         return sc, cl, mk
 
+    def _labels(self, owner, sc, cl, mk):
+        """Label images of a stage -> (label, extras or None); with NMS the workspace lives in ``owner`` (the slot, or the slot's
+        crop bucket) so that a captured graph keeps writing the memory it was captured with."""
+        if not self.use_nms:
+            return _label_image_batched(mk, instance_labels(sc, cl, **self.kw)), None
+        from . import ops
+        need = ops.mask_nms_workspace_bytes(*mk.shape)
+        if owner.get("nms_ws") is None or owner["nms_ws"].numel() < need:
+            owner["nms_ws"] = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        lab, score, bbox, count = combine_masks_with_NMS_batched(mk, sc, candidate_flags(sc, cl, **self.kw), self.nms_thresh, owner["nms_ws"])
+        return lab, dict(out_score=score, bbox=bbox, count=count)
+
     def _stage1(self, st):
         sc, cl, mk = self._predict(st["images"], st["depths"])
-        lab = _label_image_batched(mk, instance_labels(sc, cl, **self.kw))
+        lab, st["extras"] = self._labels(st, sc, cl, mk)
         if st["depths"] is not None:
             lab = filter_labels_depth(lab, st["depths"], st["thr"])
         stats, _, overflow = label_stats(lab)
@@ -704,7 +820,7 @@ class BatchedTwoStage:
         b = st["s2"][nb]
         rgb, msk, dep = ops.crop_resize(st["images"], st["depths"], st["label"], b["table"], self.crop_size)
         sc, cl, mk = self._predict(rgb, dep)
-        labels_crop = _label_image_batched(mk, instance_labels(sc, cl, **self.kw))
+        labels_crop, _ = self._labels(b, sc, cl, mk)
         raw = labels_crop.clone()
         area, bad, lab, keys = _match_pre(labels_crop, msk, dep)
         if keys is not None:
@@ -769,7 +885,7 @@ class BatchedTwoStage:
         sig = self._sig()
         if st["sig"] != sig:                                   # first use, plan switch or parameter update: re-capture everything
             st["stream"].synchronize()
-            st.update(sig=sig, g1=None, g2={}, s2={}, label=None, refs=[])
+            st.update(sig=sig, g1=None, g2={}, s2={}, label=None, refs=[], nms_ws=None, extras=None)
         with torch.cuda.stream(st["stream"]):
             st["stream"].wait_stream(torch.cuda.current_stream())
             if raw:
@@ -826,6 +942,7 @@ class BatchedTwoStage:
     def _phase3(self, st, stages=None):
         """-> (out_label (F,H,W), refined (F,H,W), rows): tensors owned by the slot (valid until its next batch)."""
         label, rows, n = st["label"], st["rows"], st["n"]
+        self.extras = st["extras"]
         if n == 0:
             return label, torch.zeros_like(label), rows
         st["ev2"].synchronize()
@@ -852,9 +969,10 @@ class BatchedTwoStage:
     def run(self, batches, consume=None):
         """Every batch of ``batches`` (lists of ``frames`` samples) through the pipeline with two batches in flight.  ``consume(i,
         out_label, refined, rows)`` is called per batch while the slot still owns the tensors; without it the results are cloned
-        into the returned list."""
+        into the returned list (and the first stage's NMS outputs, when use_nms, into ``batch_extras``)."""
         S = len(self._slots)
         results = [None] * len(batches)
+        self.batch_extras = []
 
         def finish(i):
             out = self._phase3(self._slots[i % S])
@@ -862,6 +980,8 @@ class BatchedTwoStage:
                 consume(i, *out)
             else:
                 results[i] = (out[0].clone(), out[1].clone(), out[2])
+                self.extras = None if self.extras is None else {k: v.clone() for k, v in self.extras.items()}
+                self.batch_extras.append(self.extras)
 
         for i, samples in enumerate(batches):
             if i >= 1:
