@@ -14,6 +14,8 @@
 //     K order k = lq*16 + s for both operands; a lane ends with 4 consecutive features of one token, so cmat is
 //     the accumulator's initial value (one 16-byte load) and the result leaves as one 16-byte store;
 //   * a wave holds the 16 x-values of its token tile in registers for all 16 feature blocks of the unit;
+//   * the next unit's x and the next PAIR of feature blocks' constants are requested ahead of the MFMAs that hide them, so that no wait
+//     in the loop covers a store: a unit's stores drain under the next unit's MFMAs (kv_project_body);
 //   * units are ordered image-fastest, so the 8 images of a position tile read the same cmat rows out of L2.
 // Measured (B = 8, 60x80): 36-39 us against 62-66 us for the tiled GEMM; with the MFMAs removed the kernel still
 // takes 29 us, i.e. it now sits on the 98 MB it has to move (79 MB of them written).
@@ -66,12 +68,16 @@ __device__ __forceinline__ void kv_project_body(const float* __restrict__ x, con
     auto unit_of = [&](int it) {
         return (it < full_rounds) ? it * slots + wg * KP_W + wave : full_rounds * slots + left_slot;
     };
+    // the unit loop, once per input layout (TOK: token-major x): with the layout test inside it the loop has two paths from one unit
+    // to the next, and the wait in front of a unit's first MFMA is the stricter of the two -- it drained every store
+    auto run = [&](auto tok_tag) {
+    constexpr bool TOK = decltype(tok_tag)::value;
     auto load_x = [&](int u, float (&xv)[16]) {
         const int img = (u / halves) % B, tile = u / (halves * B);
         const int p = min(tile * 16 + lj, HW - 1);
         // B operand: x[img][k = lq*16 + s][p], s = 0..15 (NCHW), or x[img][p][k] (token-major / channels-last:
         // the 16 values are four 16-byte loads)
-        if (tokens) {
+        if constexpr (TOK) {
             const float* xp = x + (int64_t)img * x_sb + (int64_t)p * KP_K + lq * 16;
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
@@ -84,35 +90,77 @@ __device__ __forceinline__ void kv_project_body(const float* __restrict__ x, con
             for (int s = 0; s < 16; ++s) xv[s] = xp[(int64_t)s * HW];
         }
     };
+    // A unit is eight PAIRS of feature blocks; each pair starts from its constants (the accumulators' initial values; SEP: the column
+    // vectors added behind the MFMAs) and ends in its two stores.  The constants are requested KP_AHEAD pairs ahead through a ring of
+    // KP_AHEAD + 1 register buffers, across the unit boundary too (the last pairs of a unit request the first of the next).  On gfx950
+    // loads and stores retire through ONE in-order counter (vmcnt), so a wait for a load also waits for every store issued before
+    // it: with the requests this far ahead the wait in front of a pair's first MFMA leaves the stores of the pairs in between
+    // outstanding, and the stores of unit i drain under the MFMAs of unit i + 1.  (All 16 constants of a unit requested at its top
+    // -- 64 registers -- sit behind the previous unit's 16 stores, and the first MFMA waits for all of them: measured 123.9 us per
+    // launch of the decoder's nine jobs at B = 8 against 118.5 us this way, docs/HISTORY.md k26 round 7.)
+    // The values do not depend on any of this: the same initial values, MFMA order and additions.
+    constexpr int NC = SEP ? 4 : 2;                          // float4s per pair: two initial values (+ two column vectors)
+    // one pair ahead (a quarter of a microsecond of this wave's MFMAs, four times that with the SIMD's other waves): the separable
+    // tables live in L2, and seven of eight units of the dense form find their rows there (units are image-fastest).  Three
+    // pairs ahead were compiled too: 128 registers and 12 - 60 bytes of scratch per lane in the forms that matter
+    constexpr int KP_AHEAD = 1;
+    constexpr int NBUF = KP_AHEAD + 1;
+    static_assert((KP_FB / 2) % NBUF == 0, "the ring index of a pair must be a compile-time constant");
+    struct UnitAddr {
+        const float *cp, *cq;
+        int tile, img, p, n_base;
+    };
+    auto unit_addr = [&](int u) {
+        UnitAddr a;
+        a.tile = u / (halves * B), a.img = (u / halves) % B;
+        a.p = min(a.tile * 16 + lj, HW - 1);                   // this lane's token, clamped: lanes past the last token repeat it (see the stores)
+        a.n_base = (u % halves) * KP_FB * 16;
+        const int py = SEP ? a.p / cw : 0;
+        a.cp = cmat + (int64_t)(SEP ? py : a.p) * N + a.n_base + lq * 4;
+        a.cq = cmat + (int64_t)(SEP ? HW / cw + (a.p - py * cw) : 0) * N + a.n_base + lq * 4;      // (SEP only)
+        return a;
+    };
+    auto load_c = [&](const UnitAddr& a, int fb, float4 (&c)[NC]) {
+        c[0] = *reinterpret_cast<const float4*>(a.cp + fb * 16);
+        c[1] = *reinterpret_cast<const float4*>(a.cp + (fb + 1) * 16);
+        if constexpr (SEP) {
+            c[2] = *reinterpret_cast<const float4*>(a.cq + fb * 16);
+            c[3] = *reinterpret_cast<const float4*>(a.cq + (fb + 1) * 16);
+        }
+    };
     float xb[16], xn[16];
-    if (mine > 0) load_x(unit_of(0), xb);
+    float4 cb[NBUF][NC];
+    UnitAddr cur, nxt;
+    if (mine > 0) {
+        cur = unit_addr(unit_of(0));
+        load_x(unit_of(0), xb);
+#pragma unroll
+        for (int j = 0; j < KP_AHEAD; ++j) load_c(cur, 2 * j, cb[j]);
+        // s_waitcnt vmcnt(0) (expcnt / lgkmcnt untouched), once: the loop is then entered with nothing outstanding, and the wait the
+        // compiler places in front of a unit's first MFMA is the one the loop's own requests need -- it leaves the last pair's
+        // stores of the previous unit in flight.  (Entered with these requests pending, that wait covers them on every trip.)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
     for (int it = 0; it < mine; ++it) {
-        const int u = unit_of(it);
-        const int half = u % halves;
-        const int tile = u / (halves * B), img = (u / halves) % B;
-        const int p = min(tile * 16 + lj, HW - 1);             // this lane's token, clamped: lanes past the last token repeat it (see the stores)
-        const int n_base = half * KP_FB * 16;
-        const int py = SEP ? p / cw : 0;
-        const float* cp = cmat + (int64_t)(SEP ? py : p) * N + n_base + lq * 4;
-        const float* cq = cmat + (int64_t)(SEP ? HW / cw + (p - py * cw) : 0) * N + n_base + lq * 4;      // (SEP only)
+        const int img = cur.img, p = cur.p, n_base = cur.n_base;
+        [[maybe_unused]] const int tile = cur.tile;           // (KP_EXP == 3)
         OT* op = out + ((int64_t)img * HW + p) * N + n_base + lq * 4;
         const float* wp = wl + (n_base + lj) * KP_LD + lq * 16;
-        // everything this unit reads from memory is requested before its first MFMA; the next unit's x rides along
-        float4 cm[KP_FB];
-#pragma unroll
-        for (int fb = 0; fb < KP_FB; ++fb) cm[fb] = *reinterpret_cast<const float4*>(cp + fb * 16);
-        load_x(unit_of(min(it + 1, mine - 1)), xn);
-        __builtin_amdgcn_sched_barrier(0);
+        // the next unit's x rides along with this unit's first pair (the last unit requests itself again: valid addresses, unused values)
+        const int un = unit_of(min(it + 1, mine - 1));
+        nxt = unit_addr(un);
+        load_x(un, xn);
+        __builtin_amdgcn_sched_barrier(0);                     // (left alone the x requests sink to the end of the unit, behind all its stores)
 #pragma unroll
         for (int fb = 0; fb < KP_FB; fb += 2) {
+            constexpr int PAIRS = KP_FB / 2;
+            const int ja = fb / 2 + KP_AHEAD;                  // the pair requested now (compile-time after unrolling)
+            if (ja < PAIRS) load_c(cur, 2 * ja, cb[ja % NBUF]);
+            else load_c(nxt, 2 * (ja - PAIRS), cb[ja % NBUF]);
+            const float4(&c)[NC] = cb[(fb / 2) % NBUF];
             // two feature blocks in flight: consecutive MFMAs alternate accumulators
-            f32x4 a0 = f32x4{cm[fb].x, cm[fb].y, cm[fb].z, cm[fb].w};
-            f32x4 a1 = f32x4{cm[fb + 1].x, cm[fb + 1].y, cm[fb + 1].z, cm[fb + 1].w};
-            float4 q0, q1;                                   // the column vectors of this pair: requested here, added after the MFMAs
-            if constexpr (SEP) {
-                q0 = *reinterpret_cast<const float4*>(cq + fb * 16);
-                q1 = *reinterpret_cast<const float4*>(cq + (fb + 1) * 16);
-            }
+            f32x4 a0 = f32x4{c[0].x, c[0].y, c[0].z, c[0].w};
+            f32x4 a1 = f32x4{c[1].x, c[1].y, c[1].z, c[1].w};
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
                 const float4 w0 = *reinterpret_cast<const float4*>(wp + fb * 16 * KP_LD + s4 * 4);
@@ -135,8 +183,8 @@ __device__ __forceinline__ void kv_project_body(const float* __restrict__ x, con
             // same values to the same address -- a branch here cuts the unit into eight basic blocks (LDS reads -> wait -> 32
             // MFMAs -> stores, nothing overlapping across them)
             if constexpr (SEP) {
-                a0 += f32x4{q0.x, q0.y, q0.z, q0.w};
-                a1 += f32x4{q1.x, q1.y, q1.z, q1.w};
+                a0 += f32x4{c[2].x, c[2].y, c[2].z, c[2].w};
+                a1 += f32x4{c[3].x, c[3].y, c[3].z, c[3].w};
             }
 #if KP_EXP == 1
             if (a0[0] == 12345.f && a1[1] == 5.f)
@@ -158,7 +206,11 @@ __device__ __forceinline__ void kv_project_body(const float* __restrict__ x, con
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) xb[s] = xn[s];
+        cur = nxt;
     }
+    };
+    if (tokens) run(std::true_type{});
+    else run(std::false_type{});
 }
 
 template <bool SEP>
