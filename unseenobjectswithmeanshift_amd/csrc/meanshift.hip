@@ -43,9 +43,8 @@ __device__ __forceinline__ unsigned int ordered_bits(float v) {
 }
 
 template <bool SMALL>
-__global__ __launch_bounds__(256) void ms_seed_step_kernel(const float* __restrict__ X, int n,
-                                                           unsigned long long* __restrict__ keys, int step,
-                                                           float* __restrict__ nearest) {
+__device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, int n, unsigned long long* __restrict__ keys, int step,
+                                                  float* __restrict__ nearest) {
     __shared__ float4 seed4[16];
     __shared__ unsigned long long red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,6 +132,23 @@ __global__ __launch_bounds__(256) void ms_seed_step_kernel(const float* __restri
         b = red[3] > b ? red[3] : b;
         if (b) atomicMax(&keys[step], b);
     }
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(256) void ms_seed_step_kernel(const float* __restrict__ X, int n,
+                                                           unsigned long long* __restrict__ keys, int step,
+                                                           float* __restrict__ nearest) {
+    ms_seed_step_body<SMALL>(X, n, keys, step, nearest);
+}
+
+// The step for M maps of one size in one launch: map = blockIdx.y, X [M][n][64], keys [M][key_stride], nearest [M][n].  A map's
+// workgroups run ms_seed_step_body on the map's own pointers, so its keys are those of the single-map launch.
+template <bool SMALL>
+__global__ __launch_bounds__(256) void ms_seed_step_batched_kernel(const float* __restrict__ X, int n,
+                                                                   unsigned long long* __restrict__ keys, int key_stride, int step,
+                                                                   float* __restrict__ nearest) {
+    const int64_t m = blockIdx.y;
+    ms_seed_step_body<SMALL>(X + m * n * MS_D, n, keys + m * key_stride, step, nearest + m * n);
 }
 
 // ---- the same step on a bf16 copy of X (precision "bf16": BASELINE configs[4], n = 1 228 800, 300 seeds) ------------------------
@@ -292,13 +308,18 @@ __device__ __forceinline__ float butterfly16(float (&p)[16], int j) {
 // most one step ahead of the slowest (its next sweep needs everybody's next store), so a slot is never overwritten before
 // every sweep of its previous use is over.  Called by one whole wave; returns the step's winner, `gave_up` set when the
 // bounded wait ran out (or another workgroup raised status[1]).
+// Grouped launches (ms_seed_persistent_grouped_kernel: several maps share one launch) confine the exchange to one map's
+// workgroups: a workgroup publishes in slot `slot0 + wg` and sweeps slots [slot0, slot0 + nwg) only, and `status` is the map's
+// own pair of words, so a group that gives up abandons its own map and nobody else's.  A whole launch is slot0 = 0,
+// nwg = gridDim.x, wg = blockIdx.x.
 __device__ __forceinline__ unsigned long long ps_exchange(unsigned long long b, int step, unsigned long long* __restrict__ gran,
-                                                          unsigned int* __restrict__ status, int lane, unsigned int& gave_up) {
+                                                          unsigned int* __restrict__ status, int lane, unsigned int& gave_up,
+                                                          int slot0, int nwg, int wg) {
     unsigned long long* ga = gran + (size_t)(step & 1) * 2 * PS_MAXWG;           // [2][PS_MAXWG]: value granules, index granules
     const unsigned long long tag = (unsigned long long)(unsigned int)step << 32;
     if (lane == 0) {
-        __hip_atomic_store(ga + blockIdx.x, tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ga + PS_MAXWG + blockIdx.x, tag | (b & 0xFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ga + slot0 + wg, tag | (b >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ga + PS_MAXWG + slot0 + wg, tag | (b & 0xFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     unsigned long long win = 0ull;
     gave_up = 0;
@@ -308,9 +329,9 @@ __device__ __forceinline__ unsigned long long ps_exchange(unsigned long long b, 
 #pragma unroll
         for (int k = 0; k < PS_MAXWG / 64; ++k) {
             const int slot = k * 64 + lane;
-            if (slot < (int)gridDim.x) {
-                const unsigned long long va = __hip_atomic_load(ga + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long vi = __hip_atomic_load(ga + PS_MAXWG + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (slot < nwg) {
+                const unsigned long long va = __hip_atomic_load(ga + slot0 + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long vi = __hip_atomic_load(ga + PS_MAXWG + slot0 + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 ok = ok && (va >> 32) == (tag >> 32) && (vi >> 32) == (tag >> 32);
                 const unsigned long long key = (va << 32) | (vi & 0xFFFFFFFFull);
                 win = key > win ? key : win;
@@ -329,17 +350,18 @@ __device__ __forceinline__ unsigned long long ps_exchange(unsigned long long b, 
     return win;
 }
 
+// `wg` of the `nwg` workgroups that hold this map; their exchange slots start at `slot0` (see ps_exchange)
 template <int NG>
-__global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_kernel(const float* __restrict__ X, int n,
-                                                                     unsigned long long* __restrict__ keys, int num_seeds,
-                                                                     unsigned int* __restrict__ status /* [1] abort */,
-                                                                     unsigned long long* __restrict__ gran /* [2][2][PS_MAXWG] */) {
+__device__ __forceinline__ void ms_seed_persistent_body(const float* __restrict__ X, int n, unsigned long long* __restrict__ keys,
+                                                        int num_seeds, unsigned int* __restrict__ status /* [1] abort */,
+                                                        unsigned long long* __restrict__ gran /* [2][2][PS_MAXWG] */, int slot0, int nwg,
+                                                        int wg) {
     __shared__ unsigned long long red[PS_W];
     __shared__ unsigned long long prev_s;
     __shared__ unsigned int abort_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, grp = lane >> 4;
-    const int blk0 = blockIdx.x * (PS_W * 4 * 16 * NG);
+    const int blk0 = wg * (PS_W * 4 * 16 * NG);
     float4 x[NG][16];
     float near[NG];
     int rowj[NG];
@@ -407,16 +429,41 @@ __global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_kernel(const flo
 #pragma unroll
             for (int w = 1; w < PS_W; ++w) b = red[w] > b ? red[w] : b;
             unsigned int gave_up;
-            const unsigned long long win = ps_exchange(b, step, gran, status, lane, gave_up);     // see ps_exchange
+            const unsigned long long win = ps_exchange(b, step, gran, status, lane, gave_up, slot0, nwg, wg);     // see ps_exchange
             if (lane == 0) {
                 abort_s = gave_up;
                 prev_s = win;                                        // the winner of this step: the next step's row
-                if (blockIdx.x == 0 && !gave_up) keys[step] = win;   // for the finish kernel (next launch)
+                if (wg == 0 && !gave_up) keys[step] = win;           // for the finish kernel (next launch)
             }
         }
         __syncthreads();
         if (abort_s != 0u) return;               // uniform per block after the barrier
     }
+}
+
+template <int NG>
+__global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_kernel(const float* __restrict__ X, int n,
+                                                                     unsigned long long* __restrict__ keys, int num_seeds,
+                                                                     unsigned int* __restrict__ status /* [1] abort */,
+                                                                     unsigned long long* __restrict__ gran /* [2][2][PS_MAXWG] */) {
+    ms_seed_persistent_body<NG>(X, n, keys, num_seeds, status, gran, 0, (int)gridDim.x, (int)blockIdx.x);
+}
+
+// ---- grouped persistent seeding: several small maps share one launch -----------------------------------------------------------
+// A 224 x 224 crop (n = 50 176) needs G = cdiv(n, 512 NG) = 33 workgroups at NG = 3: alone it pays the S - 1 dependent exchanges
+// with seven eighths of the CUs empty.  Here map `blockIdx.x / G` of the launch is held by the group of G consecutive workgroups
+// [map * G, map * G + G), `maps` <= floor(CUs / G) maps per launch, so the launch still never exceeds the CU count and every
+// workgroup is resident (the argument of ms_seed_persistent_kernel).  The groups never wait for each other: a group exchanges
+// through its own slots of `gran`, gives up through its own status words (map m: status[2 m + 1]) and writes its own keys
+// (keys [M][key_stride]).  Per row the arithmetic is ms_seed_persistent_body's, and a step's winner is a maximum over (value,
+// ~index) keys, which does not depend on how rows are split into workgroups: the indices equal the single-map launch's for any NG.
+template <int NG>
+__global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_grouped_kernel(const float* __restrict__ X, int n, int G,
+                                                                             unsigned long long* __restrict__ keys, int key_stride,
+                                                                             int num_seeds, unsigned int* __restrict__ status,
+                                                                             unsigned long long* __restrict__ gran) {
+    const int m = blockIdx.x / G, wg = blockIdx.x - m * G;      // the pointers already start at the launch's first map
+    ms_seed_persistent_body<NG>(X + (int64_t)m * n * MS_D, n, keys + (int64_t)m * key_stride, num_seeds, status + 2 * m, gran, m * G, G, wg);
 }
 
 // ---- persistent seeding over the bf16 copy for maps BEYOND the register file (round 4) ---------------------------------------
@@ -538,7 +585,7 @@ __global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_bf16_kernel(cons
 #pragma unroll
             for (int w = 1; w < PS_W; ++w) b = red[w] > b ? red[w] : b;
             unsigned int gave_up;
-            const unsigned long long win = ps_exchange(b, step, gran, status, lane, gave_up);
+            const unsigned long long win = ps_exchange(b, step, gran, status, lane, gave_up, 0, (int)gridDim.x, (int)blockIdx.x);
             if (lane == 0) {
                 abort_s = gave_up;
                 prev_s = win;
@@ -570,6 +617,36 @@ __global__ void ms_seed_finish_kernel(const float* __restrict__ X, const unsigne
         idx = 0;
     } else if (threadIdx.x == 0) sel[i] = (int64_t)idx;
     if (threadIdx.x < MS_D) seeds[(int64_t)i * MS_D + threadIdx.x] = X[(int64_t)idx * MS_D + threadIdx.x];
+}
+
+// ---- the same three for M maps: keys [M][key_stride], status [M][2], first_index [M] (device), sel [M][S], seeds [M][S][64] ----
+// gran: one [2][2][PS_MAXWG] block per persistent launch of the call (a later launch must not meet the tags of an earlier one)
+__global__ void ms_seed_status_init_batched_kernel(unsigned int* __restrict__ status, int M, unsigned long long give_up_mask,
+                                                   unsigned long long* __restrict__ gran, int64_t gran_words) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = t; i < 2 * (int64_t)M; i += nt) status[i] = (i & 1) ? (unsigned int)((give_up_mask >> ((i >> 1) & 63)) & 1ull) : 0u;
+    for (int64_t i = t; i < gran_words; i += nt) gran[i] = 0ull;
+}
+
+__global__ void ms_seed_init_batched_kernel(unsigned long long* __restrict__ keys, int key_stride, int num_seeds,
+                                            const int64_t* __restrict__ first, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
+    const int64_t f = min(max(first[m], (int64_t)0), (int64_t)n - 1);     // callers check the range; never index outside the map
+    if (i < num_seeds) keys[(int64_t)m * key_stride + i] = i == 0 ? (0xFFFFFFFF00000000ull | (unsigned long long)(0xFFFFFFFFu - (unsigned int)f)) : 0ull;
+}
+
+__global__ void ms_seed_finish_batched_kernel(const float* __restrict__ X, const unsigned long long* __restrict__ keys, int key_stride,
+                                              int64_t* __restrict__ sel, float* __restrict__ seeds, const unsigned int* __restrict__ status,
+                                              int n) {
+    const int i = blockIdx.x, S = gridDim.x;
+    const int64_t m = blockIdx.y;
+    X += m * n * MS_D;
+    unsigned int idx = 0xFFFFFFFFu - (unsigned int)(keys[m * key_stride + i] & 0xFFFFFFFFull);
+    if ((status && status[2 * m + 1] != 0u) || idx >= (unsigned int)n) {      // this map's group gave up: report, do not fabricate
+        if (threadIdx.x == 0) sel[m * S + i] = -1;
+        idx = 0;
+    } else if (threadIdx.x == 0) sel[m * S + i] = (int64_t)idx;
+    if (threadIdx.x < MS_D) seeds[(m * S + i) * MS_D + threadIdx.x] = X[(int64_t)idx * MS_D + threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -611,8 +688,8 @@ __device__ __forceinline__ void stage_points(const float* __restrict__ X, int n,
 
 // ---- hill climbing: part[wg] = sum over the workgroup's points of exp(kappa s) x ----------------
 template <int NSB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z,
-                                                      int S, float kappa, float* __restrict__ part) {
+__device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n, const float* __restrict__ Z, int S, float kappa,
+                                             float* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* zs = lds;                          // [NSB*16][SZ]
     float* xsa = lds + NSB * 16 * SZ;         // [4 waves][16][SZ]
@@ -706,6 +783,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 #undef MS_LOAD_SLAB
+
+template <int NSB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z,
+                                                      int S, float kappa, float* __restrict__ part) {
+    ms_hill_body<NSB>(X, n, Z, S, kappa, part);
+}
+
+// M maps of one size: map = blockIdx.y, the per-map grid (gridDim.x) and slab walk are the single-map launch's, so a map's
+// partials -- and after ms_hill_finish_batched_kernel its Z -- are bitwise those of msm_ms_hill_climb.  Z and part advance by
+// z_stride / part_stride floats per map.
+template <int NSB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_batched_kernel(const float* __restrict__ X, int n,
+                                                      const float* __restrict__ Z, int64_t z_stride, int S, float kappa,
+                                                      float* __restrict__ part, int64_t part_stride) {
+    const int64_t m = blockIdx.y;
+    ms_hill_body<NSB>(X + m * n * MS_D, n, Z + m * z_stride, S, kappa, part + m * part_stride);
+}
 
 // ---- the same step with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split) -----------------------------
 // Every fp32 operand is an exact sum of three bf16 terms (bf16.h: split3), a product keeps the six terms above 2^-24 of it
@@ -1249,8 +1343,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // Z[s] = normalize(sum_wg part[wg][s])  (MS:103 F.normalize).  16 waves per seed: wave w adds its fixed slice of
 // the workgroup partials (8 loads in flight), then the slices are added in wave order -- deterministic.
-__global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __restrict__ part, int nwg, int rows_padded,
-                                                              float* __restrict__ Z) {
+__device__ __forceinline__ void ms_hill_finish_body(const float* __restrict__ part, int nwg, int rows_padded, float* __restrict__ Z) {
     __shared__ float slice[16][MS_D];
     const int s = blockIdx.x, d = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int per = (nwg + 15) / 16;
@@ -1275,6 +1368,17 @@ __global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __res
     }
 }
 
+__global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __restrict__ part, int nwg, int rows_padded,
+                                                              float* __restrict__ Z) {
+    ms_hill_finish_body(part, nwg, rows_padded, Z);
+}
+
+__global__ __launch_bounds__(1024) void ms_hill_finish_batched_kernel(const float* __restrict__ part, int64_t part_stride, int nwg,
+                                                                      int rows_padded, float* __restrict__ Z, int64_t z_stride) {
+    const int64_t m = blockIdx.y;
+    ms_hill_finish_body(part + m * part_stride, nwg, rows_padded, Z + m * z_stride);
+}
+
 // ---- connected components of the converged seeds ------------------------------------------------------------------
 // mean_shift.py:41-76 is sequential and order dependent -- the i-th still-unlabelled seed claims every seed within epsilon
 // (cosine distance 0.5 (1 - z_j . z_i)); if some of those already carry labels it takes their mode (smallest label on
@@ -1284,8 +1388,8 @@ __global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __res
 // a microsecond) but the HOST: the loop used to run there on a copy of the seeds, i.e. a device synchronisation and a
 // transfer in the middle of every clustering, with the GPU idle behind it.
 constexpr int CC_MAXS = MS_SB * 16;
-__global__ __launch_bounds__(64) void ms_components_kernel(const float* __restrict__ Z, int S, float eps, int64_t* __restrict__ labels_out,
-                                                           int32_t* __restrict__ num_out) {
+__device__ __forceinline__ void ms_components_body(const float* __restrict__ Z, int S, float eps, int64_t* __restrict__ labels_out,
+                                                   int32_t* __restrict__ num_out) {
     extern __shared__ __attribute__((aligned(16))) float cz[];           // [S][MS_D + 1], then int lab[S], cnt[S]
     constexpr int ZS = MS_D + 1;
     int* lab = reinterpret_cast<int*>(cz + (size_t)S * ZS);
@@ -1355,11 +1459,22 @@ __global__ __launch_bounds__(64) void ms_components_kernel(const float* __restri
     }
 }
 
+__global__ __launch_bounds__(64) void ms_components_kernel(const float* __restrict__ Z, int S, float eps, int64_t* __restrict__ labels_out,
+                                                           int32_t* __restrict__ num_out) {
+    ms_components_body(Z, S, eps, labels_out, num_out);
+}
+
+// one wave per map: Z [M][S][64], labels_out [M][S], num_out [M][2]
+__global__ __launch_bounds__(64) void ms_components_batched_kernel(const float* __restrict__ Z, int S, float eps,
+                                                                   int64_t* __restrict__ labels_out, int32_t* __restrict__ num_out) {
+    const int64_t m = blockIdx.x;
+    ms_components_body(Z + m * S * MS_D, S, eps, labels_out + m * S, num_out + 2 * m);
+}
+
 // ---- assignment -----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ms_assign_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
-                                                        int nchunks, const int64_t* __restrict__ seed_labels,
-                                                        int64_t* __restrict__ labels_out,
-                                                        unsigned long long* __restrict__ counts, int num_labels) {
+__device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int n, const float* __restrict__ Z, int S, int nchunks,
+                                               const int64_t* __restrict__ seed_labels, int64_t* __restrict__ labels_out,
+                                               unsigned long long* __restrict__ counts, int num_labels) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int rows = nchunks * MS_CH * 16;
     float* zs = lds;                                                             // [rows][SZ]
@@ -1418,8 +1533,25 @@ __global__ __launch_bounds__(256) void ms_assign_kernel(const float* __restrict_
         if (hist[i]) atomicAdd(&counts[i], (unsigned long long)hist[i]);
 }
 
-__global__ __launch_bounds__(256) void ms_relabel_kernel(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
-                                                         int num_labels, const int32_t* __restrict__ num_alive) {
+__global__ __launch_bounds__(256) void ms_assign_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
+                                                        int nchunks, const int64_t* __restrict__ seed_labels,
+                                                        int64_t* __restrict__ labels_out,
+                                                        unsigned long long* __restrict__ counts, int num_labels) {
+    ms_assign_body(X, n, Z, S, nchunks, seed_labels, labels_out, counts, num_labels);
+}
+
+// map = blockIdx.y: X [M][n][64], Z [M][S][64], seed_labels [M][S], labels_out [M][n], counts [M][num_labels]
+__global__ __launch_bounds__(256) void ms_assign_batched_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
+                                                                int nchunks, const int64_t* __restrict__ seed_labels,
+                                                                int64_t* __restrict__ labels_out,
+                                                                unsigned long long* __restrict__ counts, int num_labels) {
+    const int64_t m = blockIdx.y;
+    ms_assign_body(X + m * n * MS_D, n, Z + m * S * MS_D, S, nchunks, seed_labels + m * S, labels_out + m * n, counts + m * num_labels,
+                   num_labels);
+}
+
+__device__ __forceinline__ void ms_relabel_body(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
+                                                int num_labels, const int32_t* __restrict__ num_alive) {
     // first argmax of counts (torch.argmax, MS:222) over labels 0 .. num - 1, num = number of distinct seed labels (MS:211-216:
     // with a vanished label the label values have gaps and the reference never counts the ones >= num); every thread
     // recomputes it (<= 304 entries)
@@ -1436,6 +1568,18 @@ __global__ __launch_bounds__(256) void ms_relabel_kernel(int64_t* __restrict__ l
         if (l == 0) labels[i] = lmax;
         else if (l == lmax) labels[i] = 0;
     }
+}
+
+__global__ __launch_bounds__(256) void ms_relabel_kernel(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
+                                                         int num_labels, const int32_t* __restrict__ num_alive) {
+    ms_relabel_body(labels, n, counts, num_labels, num_alive);
+}
+
+// map = blockIdx.y: labels [M][n], counts [M][num_labels], num_alive [M][2] (or null)
+__global__ __launch_bounds__(256) void ms_relabel_batched_kernel(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
+                                                                 int num_labels, const int32_t* __restrict__ num_alive) {
+    const int64_t m = blockIdx.y;
+    ms_relabel_body(labels + m * n, n, counts + m * num_labels, num_labels, num_alive ? num_alive + 2 * m : nullptr);
 }
 
 // whole 256-row passes per workgroup (every lane group busy), at most ~2048 atomics on the step's key
@@ -1799,5 +1943,174 @@ extern "C" int msm_ms_relabel_largest_zero(int64_t* labels, int n, const int64_t
     hipLaunchKernelGGL(ms_relabel_kernel, dim3(min(2048, cdiv(n, 256))), dim3(256), 0, (hipStream_t)stream, labels, n,
                        counts, num_labels, num_alive);
     MSM_CHECK_LAUNCH("msm_ms_relabel_largest_zero");
+    return MSM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// M maps of one size per call (the second stage of the two-stage clustering: one 224 x 224 map per object).  Exact fp32 plan only.
+// ------------------------------------------------------------------------------------------------
+static int device_cus() {
+    static int cu_cache[64] = {0};
+    int dev = 0, n_cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 64 && cu_cache[dev] > 0) return cu_cache[dev];
+    if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 64) cu_cache[dev] = n_cus;
+    return n_cus;
+}
+
+constexpr int MSB_KEYS = MS_SB * 16;           // key words per map
+constexpr int MSB_MAXM = 65535;                // maps per call (gridDim.y)
+constexpr int PSG_NG = 3;                      // 16-row tiles per lane group of the grouped launch: the fewest workgroups per map
+
+// keys [M][304] u64 | status [M][2] | gran [M][2][2][PS_MAXWG] u64 (one block per persistent launch, at most M) | nearest [M][n]
+extern "C" int64_t msm_ms_seed_batched_workspace(int M, int n) {
+    return (int64_t)M * (2 * MSB_KEYS + 2 + 2 * 4 * PS_MAXWG + (int64_t)n);
+}
+
+extern "C" int msm_ms_select_seeds_batched(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices,
+                                           float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags,
+                                           uint64_t test_give_up_mask, void* stream) {
+    MSM_REQUIRE(X && first_indices && seeds_out && indices_out && workspace, "msm_ms_select_seeds_batched: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_select_seeds_batched: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && num_seeds > 0, "msm_ms_select_seeds_batched: bad sizes (1 <= M <= %d)", MSB_MAXM);
+    MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds_batched: at most %d seeds", MS_SB * 16);
+    MSM_REQUIRE((((uintptr_t)X) & 15) == 0 && (((uintptr_t)workspace) & 7) == 0, "msm_ms_select_seeds_batched: misaligned pointer");
+    if (workspace_elems < msm_ms_seed_batched_workspace(M, n)) {
+        set_error("msm_ms_select_seeds_batched: workspace too small");
+        return MSM_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);                          // [M][MSB_KEYS]
+    unsigned int* status = reinterpret_cast<unsigned int*>(workspace + (int64_t)M * 2 * MSB_KEYS);        // [M][2]
+    unsigned long long* gran = reinterpret_cast<unsigned long long*>(workspace + (int64_t)M * (2 * MSB_KEYS + 2));
+    float* nearest = workspace + (int64_t)M * (2 * MSB_KEYS + 2 + 2 * 4 * PS_MAXWG);
+    hipLaunchKernelGGL(ms_seed_init_batched_kernel, dim3(cdiv(num_seeds, 64), M), dim3(64), 0, st, keys, MSB_KEYS, num_seeds, first_indices, n);
+    // grouped persistent launches while a map's group fits the chip (see ms_seed_persistent_grouped_kernel)
+    const int n_cus = device_cus();
+    const int G = cdiv(n, PS_W * 64 * PSG_NG);
+    const int wg_cap = min(n_cus, PS_MAXWG);
+    if (G <= wg_cap && n >= 4096 && num_seeds > 2 && !(flags & MSM_MS_SEED_STEPWISE) && opt(MSM_OPT_MS_NO_PERSISTENT) != 1) {
+        const int per = wg_cap / G;                                 // maps per launch
+        const int launches = cdiv(M, per);
+        hipLaunchKernelGGL(ms_seed_status_init_batched_kernel, dim3(min(64, cdiv(launches * 4 * PS_MAXWG, 256))), dim3(256), 0, st, status, M,
+                           (flags & MSM_MS_SEED_TEST_GIVE_UP) ? (unsigned long long)test_give_up_mask : 0ull, gran,
+                           (int64_t)launches * 4 * PS_MAXWG);
+        for (int l = 0; l < launches; ++l) {
+            const int m0 = l * per, maps = min(per, M - m0);
+            hipLaunchKernelGGL(ms_seed_persistent_grouped_kernel<PSG_NG>, dim3(maps * G), dim3(PS_W * 64), 0, st, X + (int64_t)m0 * n * MS_D, n, G,
+                               keys + (int64_t)m0 * MSB_KEYS, MSB_KEYS, num_seeds, status + 2 * m0, gran + (int64_t)l * 4 * PS_MAXWG);
+        }
+        hipLaunchKernelGGL(ms_seed_finish_batched_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, keys, MSB_KEYS, indices_out, seeds_out, status, n);
+        MSM_CHECK_LAUNCH("msm_ms_select_seeds_batched(grouped)");
+        return MSM_OK;
+    }
+    const int nblk = seed_blocks(n);
+    for (int i = 1; i < num_seeds; ++i)
+        if (n >= 16) hipLaunchKernelGGL(ms_seed_step_batched_kernel<false>, dim3(nblk, M), dim3(256), 0, st, X, n, keys, MSB_KEYS, i, nearest);
+        else hipLaunchKernelGGL(ms_seed_step_batched_kernel<true>, dim3(nblk, M), dim3(256), 0, st, X, n, keys, MSB_KEYS, i, nearest);
+    hipLaunchKernelGGL(ms_seed_finish_batched_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, keys, MSB_KEYS, indices_out, seeds_out,
+                       (const unsigned int*)nullptr, n);
+    MSM_CHECK_LAUNCH("msm_ms_select_seeds_batched");
+    return MSM_OK;
+}
+
+extern "C" int64_t msm_ms_hill_climb_batched_workspace(int M, int n, int S) { return (int64_t)M * msm_ms_hill_climb_workspace(n, S); }
+
+template <int NSB>
+static int hill_chunk_launch_batched(const float* X, int M, int n, const float* Zc, int64_t z_stride, int Sc, float kappa, float* ws,
+                                     int64_t part_stride, int G, hipStream_t st) {
+    const size_t lds = sizeof(float) * ((size_t)NSB * 16 * SZ + 4 * 16 * SZ);
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_hill_batched_kernel<NSB>, lds));
+    hipLaunchKernelGGL((ms_hill_batched_kernel<NSB>), dim3(G, M), dim3(256), lds, st, X, n, Zc, z_stride, Sc, kappa, ws, part_stride);
+    return MSM_OK;
+}
+
+extern "C" int msm_ms_hill_climb_batched(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
+                                         int64_t workspace_elems, void* stream) {
+    MSM_REQUIRE(X && Z && workspace, "msm_ms_hill_climb_batched: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_hill_climb_batched: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0,
+                "msm_ms_hill_climb_batched: bad sizes (S <= %d, M <= %d)", MS_SB * 16, MSB_MAXM);
+    MSM_REQUIRE((((uintptr_t)X) & 15) == 0, "msm_ms_hill_climb_batched: X must be 16-byte aligned");
+    if (workspace_elems < msm_ms_hill_climb_batched_workspace(M, n, S)) {
+        set_error("msm_ms_hill_climb_batched: workspace too small");
+        return MSM_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int G = hill_wgs(n);
+    const int nsb = cdiv(S, 16);
+    const int CH = hill_chunk(nsb);
+    const int64_t z_stride = (int64_t)S * MS_D, part_stride = msm_ms_hill_climb_workspace(n, S);
+    for (int it = 0; it < iters; ++it) {
+        // as msm_ms_hill_climb: all chunks of one iteration read the same Z, the finish kernels run after every chunk
+        float* ws = workspace;
+        for (int b0 = 0; b0 < nsb; b0 += CH) {
+            const int nb = min(CH, nsb - b0);
+            const float* Zc = Z + (int64_t)b0 * 16 * MS_D;
+            const int Sc = min(S - b0 * 16, nb * 16);
+            int rc = MSM_OK;
+            switch (nb) {
+                case 1: rc = hill_chunk_launch_batched<1>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 2: rc = hill_chunk_launch_batched<2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 3: rc = hill_chunk_launch_batched<3>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 4: rc = hill_chunk_launch_batched<4>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 5: rc = hill_chunk_launch_batched<5>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 6: rc = hill_chunk_launch_batched<6>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                case 7: rc = hill_chunk_launch_batched<7>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+                default: rc = hill_chunk_launch_batched<8>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
+            }
+            if (rc != MSM_OK) return rc;
+            ws += (int64_t)G * nb * 16 * MS_D;
+        }
+        ws = workspace;
+        for (int b0 = 0; b0 < nsb; b0 += CH) {
+            const int nb = min(CH, nsb - b0);
+            const int Sc = min(S - b0 * 16, nb * 16);
+            hipLaunchKernelGGL(ms_hill_finish_batched_kernel, dim3(Sc, M), dim3(1024), 0, st, ws, part_stride, G, nb * 16,
+                               Z + (int64_t)b0 * 16 * MS_D, z_stride);
+            ws += (int64_t)G * nb * 16 * MS_D;
+        }
+    }
+    MSM_CHECK_LAUNCH("msm_ms_hill_climb_batched");
+    return MSM_OK;
+}
+
+extern "C" int msm_ms_assign_batched(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
+                                     int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
+    MSM_REQUIRE(X && Z && seed_labels && labels_out && counts, "msm_ms_assign_batched: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_assign_batched: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && num_labels > 0 && num_labels <= 4096,
+                "msm_ms_assign_batched: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    MSM_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)M * (size_t)num_labels, st));
+    const int nchunks = cdiv(cdiv(S, 16), MS_CH);
+    const int G = hill_wgs(n);
+    const size_t lds = sizeof(float) * ((size_t)nchunks * MS_CH * 16 * SZ + 4 * 16 * SZ) + sizeof(unsigned int) * (size_t)num_labels;
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_batched_kernel, lds));
+    hipLaunchKernelGGL(ms_assign_batched_kernel, dim3(G, M), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
+                       reinterpret_cast<unsigned long long*>(counts), num_labels);
+    MSM_CHECK_LAUNCH("msm_ms_assign_batched");
+    return MSM_OK;
+}
+
+extern "C" int msm_ms_connected_components_batched(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
+                                                   int32_t* num_labels, void* stream) {
+    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components_batched: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components_batched: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && S > 0 && S <= CC_MAXS, "msm_ms_connected_components_batched: S=%d must be in 1..%d", S, CC_MAXS);
+    const size_t lds = sizeof(float) * (size_t)S * (MS_D + 1) + sizeof(int) * 2 * (size_t)S;
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_batched_kernel, lds));
+    hipLaunchKernelGGL(ms_components_batched_kernel, dim3(M), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
+    MSM_CHECK_LAUNCH("msm_ms_connected_components_batched");
+    return MSM_OK;
+}
+
+extern "C" int msm_ms_relabel_largest_zero_batched(int64_t* labels, int M, int n, const int64_t* counts, int num_labels,
+                                                   const int32_t* num_alive, void* stream) {
+    MSM_REQUIRE(labels && counts && M > 0 && M <= MSB_MAXM && n > 0 && num_labels > 0, "msm_ms_relabel_largest_zero_batched: bad arguments");
+    hipLaunchKernelGGL(ms_relabel_batched_kernel, dim3(min(2048, cdiv(n, 256)), M), dim3(256), 0, (hipStream_t)stream, labels, n, counts,
+                       num_labels, num_alive);
+    MSM_CHECK_LAUNCH("msm_ms_relabel_largest_zero_batched");
     return MSM_OK;
 }

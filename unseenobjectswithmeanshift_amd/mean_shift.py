@@ -135,15 +135,62 @@ def mean_shift_smart_init(X, kappa, num_seeds=100, max_iters=10, metric="cosine"
     return labels, selected
 
 
-def clustering_features(features, num_seeds=100, metric="cosine", precision="f32"):
+def mean_shift_smart_init_batched(X, kappa, num_seeds=100, max_iters=10, first_indices=None, _test_give_up=None):
+    """mean_shift_smart_init for M maps of one size in one set of launches: X (M,n,64) unit rows on the device ->
+    (labels (M,n) int64, selected (M,S) int64), each map's equal bit for bit to mean_shift_smart_init(X[m], ...,
+    first_index=first_indices[m]).  Cosine metric and the exact fp32 plan only ("f32_split" / "bf16" stay on the per-map call).
+    ``first_indices`` None draws np.random.randint(0, n) once per map, in map order, before anything is queued -- the sequence the
+    per-map loop consumes (MS:155).  Everything is queued without a host synchronisation; the one check comes last: maps whose
+    seeding group gave up (indices -1, ops.ms_select_seeds_batched) are re-run on the stepwise batched form with their recorded
+    first index, the others keep their results."""
+    X = X.contiguous()
+    M, n, _ = X.shape
+    if first_indices is None:
+        first_indices = [np.random.randint(0, n) for _ in range(M)]
+    first = ops._first_indices_device(first_indices, M, n, X.device, "mean_shift_smart_init_batched")
+
+    def chain(Xs, first, stepwise, give_up=None):
+        seeds, selected = ops.ms_select_seeds_batched(Xs, num_seeds, first, stepwise=stepwise, _test_give_up=give_up)
+        Z = ops.ms_hill_climb_batched(Xs, seeds, kappa, max_iters)
+        seed_labels, num = ops.ms_connected_components_batched(Z, 2 * EMBEDDING_ALPHA)
+        labels, counts = ops.ms_assign_batched(Xs, Z, seed_labels, num_seeds)      # num_seeds bounds the labels (see mean_shift_smart_init)
+        ops.ms_relabel_largest_zero_batched(labels, counts, num)
+        return labels, selected
+
+    labels, selected = chain(X, first, False, _test_give_up)
+    gave_up = torch.nonzero(selected.min(dim=1).values < 0).flatten()              # the one host synchronisation
+    if gave_up.numel():
+        l2, s2 = chain(X[gave_up].contiguous(), first[gave_up].contiguous(), True)
+        labels[gave_up] = l2
+        selected[gave_up] = s2
+    return labels, selected
+
+
+def clustering_features(features, num_seeds=100, metric="cosine", precision="f32", first_indices=None, map_batch=64):
     """lib/fcn/test_dataset.py:44-59: features (B,C,H,W) unit-norm along C -> (out_label (B,H,W) float,
-    selected_pixels list of (S,) index tensors).  kappa=20, 10 iterations."""
+    selected_pixels list of (S,) index tensors).  kappa=20, 10 iterations.  ``first_indices`` (not in the reference): the first
+    seed index of every map instead of np.random.randint (MS:155).  B >= 2 maps on the device with the cosine metric and
+    precision "f32" are clustered together (mean_shift_smart_init_batched), ``map_batch`` maps at a time to bound the workspace,
+    with results equal to the per-map loop's bit for bit; B = 1, "f32_split" and "bf16" take the loop."""
     B, C, H, W = features.shape
     out_label = torch.zeros((B, H, W), device=features.device)
     selected_pixels = []
+    if B >= 2 and features.is_cuda and metric == "cosine" and precision == "f32":
+        if first_indices is None:
+            first_indices = [np.random.randint(0, H * W) for _ in range(B)]      # map order, as the loop below would draw them
+        first_indices = torch.as_tensor(first_indices, dtype=torch.int64).reshape(-1).cpu()
+        for j0 in range(0, B, max(1, int(map_batch))):
+            j1 = min(B, j0 + max(1, int(map_batch)))
+            X = ops.transpose_last2(features[j0:j1].reshape(j1 - j0, C, H * W).contiguous())      # the copy is bounded by map_batch too
+            labels, sel = mean_shift_smart_init_batched(X, kappa=20, num_seeds=num_seeds, max_iters=10,
+                                                        first_indices=first_indices[j0:j1])
+            out_label[j0:j1] = labels.view(j1 - j0, H, W).float()
+            selected_pixels.extend(sel.unbind(0))
+        return out_label, selected_pixels
     for j in range(B):
         X = ops.transpose_last2(features[j].reshape(1, C, H * W).contiguous())[0]
-        labels, sel = mean_shift_smart_init(X, kappa=20, num_seeds=num_seeds, max_iters=10, metric=metric, precision=precision)
+        labels, sel = mean_shift_smart_init(X, kappa=20, num_seeds=num_seeds, max_iters=10, metric=metric, precision=precision,
+                                            first_index=None if first_indices is None else int(first_indices[j]))
         out_label[j] = labels.view(H, W).float()
         selected_pixels.append(sel)
     return out_label, selected_pixels

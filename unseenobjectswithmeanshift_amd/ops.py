@@ -1187,6 +1187,99 @@ def ms_relabel_largest_zero(labels, counts, num_alive=None):
     return labels
 
 
+# ---- M maps of one size per call (msm_ms_*_batched; exact fp32 plan only: "f32_split" / "bf16" callers keep the per-map ops) ----
+def _first_indices_device(first_indices, M, n, device, who):
+    """int64 (M,) device tensor of first seed indices.  A host sequence / array / tensor is range-checked here; a device tensor is
+    taken as it is (no host synchronisation; the kernel clamps into the map)."""
+    if torch.is_tensor(first_indices) and first_indices.is_cuda:
+        _c(first_indices, "first_indices", torch.int64)
+        if first_indices.numel() != M:
+            raise RuntimeError(f"{who}: {first_indices.numel()} first indices for {M} maps")
+        return first_indices.reshape(M)
+    host = torch.as_tensor(first_indices, dtype=torch.int64).reshape(-1)
+    if host.numel() != M:
+        raise RuntimeError(f"{who}: {host.numel()} first indices for {M} maps")
+    if int(host.min()) < 0 or int(host.max()) >= n:
+        raise RuntimeError(f"{who}: first indices must lie in [0, {n})")
+    return host.to(device)
+
+
+def ms_select_seeds_batched(X, num_seeds, first_indices, stepwise=False, _test_give_up=None):
+    """ms_select_seeds for M maps of one size: X (M,n,64) unit rows, first_indices (M,) -> (seeds (M,S,64), indices int64 (M,S)),
+    each map's bit-identical to ms_select_seeds(X[m], num_seeds, first_indices[m]).  Maps of 4096 .. 393 216 rows share grouped
+    persistent launches (a map is held by cdiv(n, 1536) workgroups, as many maps per launch as the CUs hold); a group that loses
+    co-residency reports -1 for its own map's indices only -- re-issue those maps with ``stepwise=True`` (one launch per step for
+    all maps; mean_shift.mean_shift_smart_init_batched does).  ``_test_give_up``: maps whose give-up flag starts raised (tests)."""
+    _c(X, "X")
+    M, n, d = X.shape
+    first = _first_indices_device(first_indices, M, n, X.device, "ms_select_seeds_batched")
+    seeds = torch.empty((M, num_seeds, d), device=X.device, dtype=torch.float32)
+    idx = torch.empty((M, num_seeds), device=X.device, dtype=torch.int64)
+    need = lib().msm_ms_seed_batched_workspace(M, n)
+    ws = torch.empty((need,), device=X.device, dtype=torch.float32)
+    mask = 0
+    for m in (_test_give_up or ()):
+        if not 0 <= int(m) < min(M, 64):
+            raise RuntimeError("ms_select_seeds_batched: _test_give_up names maps 0 .. min(M, 64) - 1")
+        mask |= 1 << int(m)
+    rc = lib().msm_ms_select_seeds_batched(_p(X), M, n, d, num_seeds, _p(first), _p(seeds), _p(idx), _p(ws), need,
+                                           (1 if stepwise else 0) | (2 if mask else 0), mask, _stream())
+    check(rc, "msm_ms_select_seeds_batched")
+    return seeds, idx
+
+
+def ms_hill_climb_batched(X, Z, kappa, iters):
+    """ms_hill_climb (precision "f32") for M maps: X (M,n,64), Z (M,S,64) -> the updated copy of Z, each map's bitwise equal to
+    ms_hill_climb(X[m], Z[m], kappa, iters) (same per-map grid, slab walk and summation order)."""
+    _c(X, "X"), _c(Z, "Z")
+    M, n, d = X.shape
+    if Z.dim() != 3 or Z.shape[0] != M or Z.shape[2] != d:
+        raise RuntimeError(f"ms_hill_climb_batched: Z has shape {tuple(Z.shape)}, expected ({M}, S, {d})")
+    S = Z.shape[1]
+    Z = Z.clone()
+    need = lib().msm_ms_hill_climb_batched_workspace(M, n, S)
+    ws = torch.empty((need,), device=X.device, dtype=torch.float32)
+    check(lib().msm_ms_hill_climb_batched(_p(X), M, n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()),
+          "msm_ms_hill_climb_batched")
+    return Z
+
+
+def ms_assign_batched(X, Z, seed_labels, num_labels):
+    """ms_assign for M maps: X (M,n,64), Z (M,S,64), seed_labels int64 (M,S) -> (labels int64 (M,n), counts int64 (M,num_labels))."""
+    _c(X, "X"), _c(Z, "Z"), _c(seed_labels, "seed_labels", torch.int64)
+    M, n, d = X.shape
+    if Z.dim() != 3 or Z.shape[0] != M or Z.shape[2] != d or tuple(seed_labels.shape) != tuple(Z.shape[:2]):
+        raise RuntimeError(f"ms_assign_batched: Z {tuple(Z.shape)} / seed_labels {tuple(seed_labels.shape)} do not match X {tuple(X.shape)}")
+    labels = torch.empty((M, n), device=X.device, dtype=torch.int64)
+    counts = torch.empty((M, num_labels), device=X.device, dtype=torch.int64)
+    rc = lib().msm_ms_assign_batched(_p(X), M, n, d, _p(Z), Z.shape[1], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
+    check(rc, "msm_ms_assign_batched")
+    return labels, counts
+
+
+def ms_connected_components_batched(Z, epsilon):
+    """ms_connected_components for M seed sets, one wave each: Z (M,S,64) -> (seed_labels int64 (M,S), num int32 (M,2))."""
+    _c(Z, "Z")
+    M, S, d = Z.shape
+    seed_labels = torch.empty((M, S), device=Z.device, dtype=torch.int64)
+    num = torch.empty((M, 2), device=Z.device, dtype=torch.int32)
+    check(lib().msm_ms_connected_components_batched(_p(Z), M, S, d, float(epsilon), _p(seed_labels), _p(num), _stream()),
+          "msm_ms_connected_components_batched")
+    return seed_labels, num
+
+
+def ms_relabel_largest_zero_batched(labels, counts, num_alive=None):
+    """ms_relabel_largest_zero per map, in place: labels int64 (M,n), counts int64 (M,num_labels), num_alive int32 (M,2)
+    (ms_connected_components_batched()[1]) or None."""
+    _c(labels, "labels", torch.int64), _c(counts, "counts", torch.int64), _c(num_alive, "num_alive", torch.int32)
+    M, n = labels.shape
+    if counts.dim() != 2 or counts.shape[0] != M or (num_alive is not None and tuple(num_alive.shape) != (M, 2)):
+        raise RuntimeError("ms_relabel_largest_zero_batched: counts must be (M, num_labels) and num_alive (M, 2)")
+    rc = lib().msm_ms_relabel_largest_zero_batched(_p(labels), M, n, _p(counts), counts.shape[1], _p(num_alive), _stream())
+    check(rc, "msm_ms_relabel_largest_zero_batched")
+    return labels
+
+
 # ----------------------------------------------------------------------------------------------
 # instance post-processing (pretrained_meanshiftformer_model.py:337-343, 461-497)
 # ----------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@ return values:
   test_dataset(_crop)       <- lib/fcn/test_utils.py:424-513   (the printed means, returned)
   test_batch_crop           the labelled form of test_batch_crop_nolabel (one metrics call per batch)
   combine_masks_with_NMS_batched  nms + combine_masks_with_NMS for a batch of images without compaction or host round trip
+  test_sample_clustering    <- lib/fcn/test_dataset.py:232-267  (the UCN method: embedding network -> mean-shift clustering, both stages)
+  test_batch_clustering     the same for a batch of frames: every second-stage map of the batch clustered in one batched call
 
 These are data-dependent, tiny (<= 20 instances) bookkeeping steps; they run as torch ops on
 whatever device the label maps live on (GPU in production, CPU in the unit tests), never through
@@ -994,3 +996,133 @@ class BatchedTwoStage:
         for i in range(max(0, len(batches) - S), len(batches)):
             finish(i)
         return None if consume is not None else results
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The UCN two-stage method (lib/fcn/test_dataset.py:232-267): what the seg_resnet34_8s_embedding checkpoints (checkpoint.py ->
+# UCNBackbone) are for.  Embedding network -> vMF mean-shift clustering -> depth filter -> ROI crops -> the crop network on the
+# 224 x 224 crops -> clustering of every crop -> paste back.  The second stage clusters one small map per object; on the device
+# all of them go through ONE batched clustering (mean_shift.clustering_features -> mean_shift_smart_init_batched).
+# ----------------------------------------------------------------------------------------------------------------------
+def _cluster_fn(cluster, features):
+    if cluster is not None:
+        return cluster
+    if not features.is_cuda:
+        raise RuntimeError("the clustering has no CPU path in unseenobjectswithmeanshift_amd: pass cluster= (e.g. the oracle's "
+                           "clustering_features) for host tensors")
+    from . import mean_shift
+    return mean_shift.clustering_features
+
+
+def _take_first(first_indices, k, what):
+    if k >= len(first_indices):
+        raise ValueError(f"first_indices holds {len(first_indices)} indices, {what} needs one more (the first stage's, then one per crop)")
+    return int(first_indices[k])
+
+
+def test_sample_clustering(sample, network, network_crop=None, *, num_seeds=100, depth_threshold=0.8, first_indices=None, cluster=None,
+                           stages=None):
+    """lib/fcn/test_dataset.py:232-267, step for step -> (out_label (1,H,W), out_label_refined (1,H,W) or None).
+    sample: {"image_color" (1,3,H,W), "depth" (1,3,H,W) xyz (optional: no depth, no depth filter), "label" (optional)};
+    ``network(image, label, depth)`` returns unit-norm embeddings (1,C,H,W), ``network_crop(rgb_crop, mask_crop, depth_crop)``
+    (N,C,224,224).  ``first_indices``: the first seed index of the first stage's map, then one per crop in ascending label order,
+    in place of the reference's np.random.randint draws (MS:155), which are made here, in that order, when it is None.
+    ``cluster``: the clustering_features to use -- default mean_shift.clustering_features on device tensors (the crops in one batched
+    call); host tensors (the CPU tests of this logic) must pass one, e.g. the oracle's.  ``stages``: a dict that receives the
+    intermediate tensors (selected indices, ROIs, per-crop label images) -- for tests."""
+    image = sample["image_color"]
+    depth = sample.get("depth")
+    label = sample.get("label")
+    H, W = image.shape[-2:]
+    features = network(image, label, depth).detach()                                             # TD:247
+    cluster = _cluster_fn(cluster, features)
+    first = np.random.randint(0, H * W) if first_indices is None else _take_first(first_indices, 0, "the first stage")
+    out_label, selected_pixels = cluster(features, num_seeds=num_seeds, first_indices=[first])   # TD:248
+    raw_label = out_label
+    if depth is not None:
+        out_label = filter_labels_depth(out_label, depth, depth_threshold)                       # TD:252
+    out_label_refined = None
+    if stages is not None:
+        stages.update(label=raw_label, selected=selected_pixels, rois=None, labels_crop=None, selected_crop=[])
+    if network_crop is not None:
+        rgb_crop, out_label_crop, rois, depth_crop = crop_rois(image, out_label.clone(), depth)  # TD:257
+        n = rgb_crop.shape[0]
+        if n > 0:
+            features_crop = network_crop(rgb_crop, out_label_crop, depth_crop).detach()          # TD:259
+            hw = features_crop.shape[-2] * features_crop.shape[-1]
+            firsts = [np.random.randint(0, hw) if first_indices is None else _take_first(first_indices, 1 + i, f"crop {i}") for i in range(n)]
+            labels_crop, selected_crop = cluster(features_crop, num_seeds=num_seeds, first_indices=firsts)      # TD:260
+            labels_crop = labels_crop.to(out_label.device)
+            out_label_refined, labels_crop = match_label_crop(out_label, labels_crop, out_label_crop, rois, depth_crop)   # TD:261
+            if stages is not None:
+                stages.update(rois=rois, labels_crop=labels_crop, selected_crop=selected_crop)      # rejected segments are -1
+    return out_label, out_label_refined
+
+
+def test_batch_clustering(samples, network, network_crop=None, *, num_seeds=100, depth_threshold=0.8, first_indices=None, crop_batch=256,
+                          cluster=None, stages=None):
+    """test_sample_clustering for a list of F frames of one size -> (out_label (F,H,W), refined (F,H,W) or None, rows); frame f's
+    results equal test_sample_clustering(samples[f], ...)[0][0] / [1][0] given the same first indices (the reference crops image 0
+    of its batch only, so its batch is always 1: the semantics stay per frame).  ``rows`` is the ROI table (frame, label, x0, y0,
+    x1, y1, 0, 0) of the second stage.
+    The first stage clusters the F maps in one call (at 640 x 480 a map's workgroups fill more than half of the chip, so the
+    grouped seeding carries one map per launch); the second stage cuts every ROI of every frame in one launch, runs ``network_crop``
+    on ``crop_batch`` crops at a time, clusters ALL N crops of the batch in one batched call and pastes every frame in one launch.
+    ``first_indices``: per frame the sequence test_sample_clustering takes (first stage, then the frame's crops); None draws them
+    with np.random.randint -- the F first-stage indices, then the crops' in (frame, label) order."""
+    Fr = len(samples)
+    images = torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples]).float().contiguous()
+    with_depth = [s.get("depth") is not None for s in samples]
+    if any(with_depth) and not all(with_depth):
+        raise ValueError("either every frame of a batch has \"depth\" or none")
+    depths = None
+    if Fr and with_depth[0]:
+        depths = torch.stack([s["depth"][0] if s["depth"].dim() == 4 else s["depth"] for s in samples]).float().contiguous()
+    labels = None
+    if all("label" in s for s in samples):
+        labels = torch.stack([torch.as_tensor(s["label"]).reshape(s["label"].shape[-2:]) for s in samples])
+    _, _, H, W = images.shape
+    features = network(images, labels, depths).detach()
+    cluster = _cluster_fn(cluster, features)
+    if first_indices is not None and len(first_indices) != Fr:
+        raise ValueError(f"first_indices must hold one sequence per frame ({Fr}), got {len(first_indices)}")
+    firsts = [np.random.randint(0, H * W) if first_indices is None else _take_first(first_indices[f], 0, f"frame {f}'s first stage")
+              for f in range(Fr)]
+    out_label, selected_pixels = cluster(features, num_seeds=num_seeds, first_indices=firsts)
+    if stages is not None:
+        stages.update(label=out_label, selected=selected_pixels, labels_crop=None, selected_crop=[])
+    if depths is not None:
+        out_label = filter_labels_depth(out_label, depths, depth_threshold)
+    if network_crop is None:
+        return out_label, None, []
+    stats, _, overflow = label_stats(out_label)
+    packed = torch.cat([stats.reshape(-1), overflow]).cpu().numpy()                      # the batch's first transfer
+    rows = roi_table(packed[:-Fr].reshape(Fr, -1, 5), packed[-Fr:], H, W)
+    n = len(rows)
+    if n == 0:
+        return out_label, torch.zeros_like(out_label), rows
+    rgb_crop, mask_crop, depth_crop = _crop_resize_batched(images, depths, out_label, rows, CROP_SIZE)
+    # the N crop embeddings (12.8 MB each at 64 x 224 x 224) are the one buffer of size N: chunks are written into it as they come, and
+    # the clustering transposes map_batch maps at a time (mean_shift.clustering_features)
+    features_crop = None
+    for c0 in range(0, n, crop_batch):
+        part = network_crop(rgb_crop[c0:c0 + crop_batch], mask_crop[c0:c0 + crop_batch],
+                            None if depth_crop is None else depth_crop[c0:c0 + crop_batch]).detach()
+        if features_crop is None:
+            features_crop = part if part.shape[0] == n else part.new_empty((n,) + tuple(part.shape[1:]))
+        if features_crop is not part:
+            features_crop[c0:c0 + part.shape[0]] = part
+        del part
+    hw = features_crop.shape[-2] * features_crop.shape[-1]
+    seen = [0] * Fr
+    crop_firsts = []
+    for r in rows:                                                                       # (frame, ascending label) order
+        seen[r[0]] += 1
+        crop_firsts.append(np.random.randint(0, hw) if first_indices is None
+                           else _take_first(first_indices[r[0]], seen[r[0]], f"frame {r[0]}'s crop {seen[r[0]] - 1}"))
+    labels_crop, selected_crop = cluster(features_crop, num_seeds=num_seeds, first_indices=crop_firsts)      # ONE call for the N crops
+    labels_crop = labels_crop.to(out_label.device)
+    refined = match_label_crop_batched(out_label, labels_crop, mask_crop, rows, depth_crop)
+    if stages is not None:
+        stages.update(rgb_crop=rgb_crop, mask_crop=mask_crop, depth_crop=depth_crop, labels_crop=labels_crop, selected_crop=selected_crop)
+    return out_label, refined, rows
