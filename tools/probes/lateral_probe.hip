@@ -1,7 +1,8 @@
 // Where do the 64 us of the FPN lateral (x NCHW 8 x 256 x 19200 fp32 -> 64 channels, K = 256) go?  The product kernel's structure
 // (one 32-pixel tile per wave over the full K, ring of 4 k-groups) with parts switched off:
 //   MODE 0 as shipped; 1 no MFMAs (loads only, xor-summed); 2 no x loads (MFMAs on stale registers); 3 x read as if it were
-//   tile-major ([tile][k][32 pixels]: the same bytes, linear per wave) to price the NCHW stride pattern; 4 no loads in the loop.
+//   tile-major ([tile][k][32 pixels]: the same bytes, linear per wave) to price the NCHW stride pattern; 4 no loads in the loop;
+//   5 no weight loads (x loads kept, MFMAs on stale weight registers): what a weight resident in LDS could at most take off.
 //   hipcc --offload-arch=gfx950 -O3 tools/probes/lateral_probe.hip -o /tmp/lateral_probe && /tmp/lateral_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -30,10 +31,12 @@ __global__ __launch_bounds__(512, 4) void lateral(const float* __restrict__ x, c
     float wa[D][4][2], xa[D][NT][2];
     auto load = [&](int kg, float (&wf)[4][2], float (&xf)[NT][2]) {
         if (MODE == 4) return;
+        if (MODE != 5) {
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(wr, wo, (unsigned)(kg * 4 + mt) * 512u, 0);
-            wf[mt][0] = __uint_as_float(t.x); wf[mt][1] = __uint_as_float(t.y);
+            for (int mt = 0; mt < 4; ++mt) {
+                const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(wr, wo, (unsigned)(kg * 4 + mt) * 512u, 0);
+                wf[mt][0] = __uint_as_float(t.x); wf[mt][1] = __uint_as_float(t.y);
+            }
         }
         if (MODE == 2) return;
 #pragma unroll
@@ -108,6 +111,8 @@ int main() {
     run<2>("no x loads", x, w, out, B, Cin, HW);
     run<3>("x as tile-major (linear per wave)", x, w, out, B, Cin, HW);
     run<4>("no loads in the loop at all (MFMAs + stores)", x, w, out, B, Cin, HW);
+    run<5>("no weight loads (x loads + MFMAs + stores)", x, w, out, B, Cin, HW);
     run<0>("as shipped (again)", x, w, out, B, Cin, HW);
+    run<5>("no weight loads (again)", x, w, out, B, Cin, HW);
     return 0;
 }

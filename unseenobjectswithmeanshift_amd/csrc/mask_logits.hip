@@ -30,6 +30,8 @@ namespace msm {
 
 constexpr int QB = 7;           // 16-row MFMA blocks per query chunk
 constexpr int QCH = QB * 16;    // 112 queries per chunk
+constexpr int QBS = 2;          // ... of the fp32 kernel's short form: launches of at most 32 queries that write the logits
+                                // (the final step on the kept top-K rows) multiply two blocks instead of two and five of zeros
 #ifndef MSM_MASK_KU
 #define MSM_MASK_KU 4
 #endif
@@ -112,8 +114,8 @@ struct PixMap {
     }
 };
 
-template <int NC>
-__device__ __forceinline__ float acc_val(const f32x4 (&acc)[QB][2 * NC], int m, int row, int j) {
+template <int NC, int NQ>
+__device__ __forceinline__ float acc_val(const f32x4 (&acc)[NQ][2 * NC], int m, int row, int j) {
     if constexpr (NC == 2) return acc[m][row * 2 + (j & 1)][j >> 1];
     else return acc[m][row][j];
 }
@@ -121,8 +123,8 @@ __device__ __forceinline__ float acc_val(const f32x4 (&acc)[QB][2 * NC], int m, 
 // Generic per-tile epilogue shared by the fp32 and bf16 kernels (see the layout note above): any tile (partly outside the
 // map, unaligned rows, permuted pixels).  c0: first column of the tile; DO_WRITE / DO_ATTN select the two halves so that a
 // kernel can take the fast path (mask_tile_epilogue_fast below) for one and this one for the other.
-template <int POOL, bool WRITE, int NC, bool DO_WRITE = true, bool DO_ATTN = true, bool R4 = false>
-__device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[QB][2 * NC], float* __restrict__ mask_out,
+template <int POOL, bool WRITE, int NC, bool DO_WRITE = true, bool DO_ATTN = true, bool R4 = false, int NQ = QB>
+__device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[NQ][2 * NC], float* __restrict__ mask_out,
                                                    uint8_t* __restrict__ attn_out, int* __restrict__ any_flags, int b, int Q,
                                                    int q0, int H, int W, int th, int tw, int ytop, int ybot, int c0, int lj, int lq) {
     using PM = PixMap<POOL, NC>;
@@ -134,9 +136,9 @@ __device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[QB][2 * NC
     const int xb = c0 + NP * lq;                     // first column of this lane (identity mapping)
     if constexpr (WRITE && DO_WRITE) {
 #pragma unroll
-        for (int m = 0; m < QB; ++m) {
+        for (int m = 0; m < NQ; ++m) {
             // (R4: in the 4-query block lane lj of the lq == 0 quarter holds query 96 + (lj & 3) and pixel group lj >> 2)
-            const bool rem = R4 && m == QB - 1;
+            const bool rem = R4 && m == NQ - 1;
             const int pg = rem ? (ql >> 2) : lq;
             const int xb = c0 + NP * pg;
             const bool vec = !PM::PERM && xb + NP <= W && (W & 3) == 0;   // 16-byte aligned rows, whole lane inside the map
@@ -170,7 +172,7 @@ __device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[QB][2 * NC
         const int HW = H * W;
         const bool vec = xb + NP <= W && (W & 3) == 0;
 #pragma unroll
-        for (int m = 0; m < QB; ++m) {
+        for (int m = 0; m < NQ; ++m) {
             const int q = q0 + m * 16 + ql;
             if (q >= Q) continue;
             uint8_t* o = attn_out + ((int64_t)b * Q + q) * HW;
@@ -214,7 +216,7 @@ __device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[QB][2 * NC
         static_assert(PM::PERM || NP >= POOL, "a lane must hold whole taps");
         const bool vec = NT == 4 ? ((tw & 3) == 0 && tx0 + 4 <= tw) : (NT == 2 ? ((tw & 1) == 0 && tx0 + 2 <= tw) : (tx0 < tw));
 #pragma unroll
-        for (int m = 0; m < QB; ++m) {
+        for (int m = 0; m < NQ; ++m) {
             uint32_t w = 0;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -250,11 +252,11 @@ __device__ __forceinline__ void mask_tile_epilogue(const f32x4 (&acc)[QB][2 * NC
 // 16-query block) in the attention-mask and mask outputs of image b, relative to buffer descriptors over that image's
 // outputs.  Rows q >= Q get offsets beyond the descriptor's size: the hardware drops those stores, so the tile loop has no
 // per-lane bounds logic at all; the per-tile part of the address (row, first column) is wave-uniform and travels in SGPRs.
-template <int POOL, bool WRITE, int NC>
+template <int POOL, bool WRITE, int NC, int NQ = QB>      // NQ: query blocks of the chunk (QB, or QBS in the short fp32 form)
 struct MaskEpiConst {
-    unsigned aoff[QB];     // attention mask: (q * TT + lane's first key) bytes, TT = keys per query
-    unsigned moff[QB];     // mask logits: (q * H*W + lane's first pixel) * 4 bytes
-    unsigned anyv[QB];     // != 0 once a key of the row was seen attendable
+    unsigned aoff[NQ];     // attention mask: (q * TT + lane's first key) bytes, TT = keys per query
+    unsigned moff[NQ];     // mask logits: (q * H*W + lane's first pixel) * 4 bytes
+    unsigned anyv[NQ];     // != 0 once a key of the row was seen attendable
     __amdgpu_buffer_rsrc_t arsrc, mrsrc;
     bool attn_fast, write_fast;      // kernel-uniform: the alignment conditions of the vector stores hold
 };
@@ -278,8 +280,8 @@ __device__ __forceinline__ void* uniform_ptr64(const void* p) {
 
 // r4: the chunk is 6 full query blocks + 4 queries and block 6 is multiplied on v_mfma_f32_4x4x1_16b_f32 (see mask_logits_kernel):
 // there lane lj of the lq == 0 quarter holds query 96 + (lj & 3) and the pixels of group lj >> 2 (the role lq plays in a full block)
-template <int POOL, bool WRITE, int NC>
-__device__ __forceinline__ void mask_epi_init(MaskEpiConst<POOL, WRITE, NC>& k, float* mask_out, uint8_t* attn_out, int b, int Q, int q0,
+template <int POOL, bool WRITE, int NC, int NQ>
+__device__ __forceinline__ void mask_epi_init(MaskEpiConst<POOL, WRITE, NC, NQ>& k, float* mask_out, uint8_t* attn_out, int b, int Q, int q0,
                                               int H, int W, int th, int tw, int lj, int lq, bool r4 = false) {
     using PM = PixMap<POOL, NC>;
     constexpr int NP = 4 * NC;
@@ -287,8 +289,8 @@ __device__ __forceinline__ void mask_epi_init(MaskEpiConst<POOL, WRITE, NC>& k, 
     const int TT = POOL == 1 ? HW : th * tw;
     constexpr int NT = PM::PERM ? 1 : (POOL == 1 ? NP : (NP / (POOL > 0 ? POOL : 1) > 0 ? NP / (POOL > 0 ? POOL : 1) : 1));
 #pragma unroll
-    for (int m = 0; m < QB; ++m) {
-        const bool rem = r4 && m == QB - 1;
+    for (int m = 0; m < NQ; ++m) {
+        const bool rem = r4 && m == NQ - 1;
         const int pgl = rem ? (lj >> 2) : lq;                  // pixel group of the lane: lq, or lj >> 2 in the 4-query block
         const int q = rem ? q0 + m * 16 + (lj & 3) : q0 + m * 16 + lj;
         // first key of the lane inside a tile row
@@ -314,11 +316,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // offset --, the row_any flags are OR-ed into registers and reach LDS once per kernel.  VALU instructions next to a busy
 // MFMA pipe are expensive (the sibling wave of the SIMD is in its K loop): measured with in-kernel timestamps, the generic
 // epilogue cost 1.8 (15x20 / 30x40 targets) to 3.5 us (60x80) per 3 us tile, this one a few hundred ns.
-// R4_PARTIAL: block QB - 1 holds per-channel-class PARTIAL sums (4-query block on the 4x4x1 MFMA, see mask_logits_kernel): the tap
+// R4_PARTIAL: block NQ - 1 holds per-channel-class PARTIAL sums (4-query block on the 4x4x1 MFMA, see mask_logits_kernel): the tap
 // sum is linear, so it is formed on the partials and the four classes (lanes l ^ 16, l ^ 32) are added afterwards -- two values per
 // tile and lane at POOL 2, one at 4 / 8, instead of all eight accumulators.
-template <int POOL, bool WRITE, int NC, bool DO_WRITE, bool DO_ATTN, bool R4_PARTIAL = false>
-__device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2 * NC], MaskEpiConst<POOL, WRITE, NC>& k, int H, int W, int tw,
+template <int POOL, bool WRITE, int NC, bool DO_WRITE, bool DO_ATTN, bool R4_PARTIAL = false, int NQ = QB>
+__device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[NQ][2 * NC], MaskEpiConst<POOL, WRITE, NC, NQ>& k, int H, int W, int tw,
                                                         int ytop, int ybot, int c0) {
     using PM = PixMap<POOL, NC>;
     constexpr int NP = 4 * NC;
@@ -336,7 +338,7 @@ __device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2
             if (y < 0 || y >= H) continue;                                  // wave-uniform
             const unsigned soff = (unsigned)(y * W + c0) * 4u;
 #pragma unroll
-            for (int m = 0; m < QB; ++m)
+            for (int m = 0; m < NQ; ++m)
 #pragma unroll
                 for (int j = 0; j < NP; j += 4)
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(acc_val<NC>(acc, m, row, j)), __float_as_uint(acc_val<NC>(acc, m, row, j + 1)),
@@ -353,7 +355,7 @@ __device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2
             if (y < 0 || y >= H) continue;
             const unsigned soff = (unsigned)(y * W + c0);
 #pragma unroll
-            for (int m = 0; m < QB; ++m)
+            for (int m = 0; m < NQ; ++m)
 #pragma unroll
                 for (int j0 = 0; j0 < NP; j0 += 4) {
                     unsigned w = 0;
@@ -371,7 +373,7 @@ __device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2
         static_assert(PM::PERM || NP >= POOL, "a lane must hold whole taps");
         const unsigned soff = (unsigned)((ytop / POOL) * tw + c0 / POOL);
 #pragma unroll
-        for (int m = 0; m < QB; ++m) {
+        for (int m = 0; m < NQ; ++m) {
             unsigned w = 0;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -379,7 +381,7 @@ __device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2
                 float s = add1(add1(acc_val<NC>(acc, m, 0, jl), acc_val<NC>(acc, m, 0, jl + 1)),
                                add1(acc_val<NC>(acc, m, 1, jl), acc_val<NC>(acc, m, 1, jl + 1)));
                 if constexpr (R4_PARTIAL) {
-                    if (m == QB - 1) {
+                    if (m == NQ - 1) {
                         s = sum_lane_rows(s);
                     }
                 }
@@ -409,12 +411,12 @@ __device__ __forceinline__ void mask_tile_epilogue_fast(const f32x4 (&acc)[QB][2
 }
 
 // flags collected by the fast path -> LDS (the generic path writes LDS directly); rows / lanes that never stored keep 0
-template <int POOL, bool WRITE, int NC>
-__device__ __forceinline__ void mask_epi_flush(const MaskEpiConst<POOL, WRITE, NC>& k, int* __restrict__ any_flags, int lj, bool r4 = false) {
+template <int POOL, bool WRITE, int NC, int NQ>
+__device__ __forceinline__ void mask_epi_flush(const MaskEpiConst<POOL, WRITE, NC, NQ>& k, int* __restrict__ any_flags, int lj, bool r4 = false) {
     if constexpr (POOL != 0) {
 #pragma unroll
-        for (int m = 0; m < QB; ++m)
-            if (k.anyv[m] != 0u && k.aoff[m] != 0xF0000000u) any_flags[m * 16 + ((r4 && m == QB - 1) ? (lj & 3) : lj)] = 1;
+        for (int m = 0; m < NQ; ++m)
+            if (k.anyv[m] != 0u && k.aoff[m] != 0xF0000000u) any_flags[m * 16 + ((r4 && m == NQ - 1) ? (lj & 3) : lj)] = 1;
     }
 }
 
@@ -422,7 +424,7 @@ __device__ __forceinline__ void mask_epi_flush(const MaskEpiConst<POOL, WRITE, N
 // meanshiftformer_transformer_decoder.py:1012-1035 with target size == mask size: interpolate is the
 // identity); 2/4/8 = 2x2-tap average of a bilinear downsample by that factor.
 // D: depth of the feature prefetch ring in groups of KU k-steps (G = C / (4 KU) must be a multiple of D).
-template <int POOL, bool WRITE, int NC, int D, bool R4 = false>
+template <int POOL, bool WRITE, int NC, int D, bool R4 = false, int NQ = QB>
 __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __restrict__ emb, const float* __restrict__ feat,
                                                           float* __restrict__ mask_out, uint8_t* __restrict__ attn_out,
                                                           int32_t* __restrict__ row_any, int Q, int C, int H, int W,
@@ -431,6 +433,7 @@ __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __res
                                                           const float* __restrict__ qbias, int64_t qbias_ld) {
     extern __shared__ __attribute__((aligned(16))) float Es[];   // [QCH][C + 2] embeddings, then [QCH] per-query biases
     constexpr int TW = 16 * NC;      // tile width in columns
+    constexpr int QCH = NQ * 16;     // queries per chunk of THIS instantiation (shadows the seven-block constant)
     constexpr int NA = 2 * NC;       // accumulator pixel blocks: [row (top,bottom)][cc]
     const int SE = C + 2;
     const int b = blockIdx.z, qc = blockIdx.y;
@@ -541,19 +544,19 @@ __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __res
     // per-lane constants: the bias of the lane's query of every block as a ready-made accumulator tuple (the first MFMA of a
     // tile takes it as its C operand: no accumulator initialisation instructions), the store offsets of the fast epilogue
     // (NC == 1 only: with 2 x 32 tiles the 28 registers do not fit next to 112 accumulators, the tuples are rebuilt per tile)
-    constexpr int NB4 = NC == 1 ? QB : 1;
+    constexpr int NB4 = NC == 1 ? NQ : 1;
     f32x4 bias4[NB4];
     if constexpr (NC == 1) {
 #pragma unroll
-        for (int m = 0; m < QB; ++m) {
+        for (int m = 0; m < NQ; ++m) {
             float q_b = qb[m * 16 + lj];
-            if (R4 && m == QB - 1) q_b = lq == 0 ? qb[m * 16 + (lj & 3)] : 0.f;   // 4-query block: the four channel classes lq are
+            if (R4 && m == NQ - 1) q_b = lq == 0 ? qb[m * 16 + (lj & 3)] : 0.f;   // 4-query block: the four channel classes lq are
                                                                                   // summed at the end, the bias enters once
             bias4[m] = f32x4{q_b, q_b, q_b, q_b};
         }
     }
     static_assert(!R4 || NC == 1, "the 4-query block exists for 2 x 16 tiles only");
-    MaskEpiConst<POOL, WRITE, NC> epi;
+    MaskEpiConst<POOL, WRITE, NC, NQ> epi;
     mask_epi_init<POOL, WRITE, NC>(epi, mask_out, attn_out, b, Q, q0, H, W, th, tw, lj, lq, R4);
 
     const int G = C / (4 * KU);          // even and >= 2: C is a multiple of 32
@@ -575,15 +578,15 @@ __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __res
         unsigned nvoff_top, nvoff_bot;
         tile_voffs(tile_of(min(it + 1, my_tiles - 1)), nvoff_top, nvoff_bot);   // the last tile re-reads its own first group
 
-        f32x4 acc[QB][NA];
+        f32x4 acc[NQ][NA];
         auto compute_group = [&](auto first, const Cols<NC>(&t_)[KU], const Cols<NC>(&bt)[KU], int kbase) {
 #pragma unroll
             for (int u = 0; u < KU; ++u) {
                 const float* er = &Es[lj * SE + kbase + u * 4 + lq];
 #pragma unroll
-                for (int m = 0; m < QB; ++m) {
+                for (int m = 0; m < NQ; ++m) {
                     if constexpr (R4) {
-                        if (m == QB - 1) {
+                        if (m == NQ - 1) {
                             // Q = 96 + 4: the last block holds four queries.  v_mfma_f32_4x4x1_16b_f32 = sixteen 4 x 4 x 1 products
                             // (block = lane / 4; 8 cycles instead of 32): with this A operand block (lq, lj >> 2) is the four
                             // pixels 4 (lj >> 2) .. + 3 at channel 4 u + lq, so B = mask_embed[96 + (lj & 3)][4 u + lq] gives
@@ -640,7 +643,7 @@ __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __res
         MASK_TS(2 + 3 * it)
 #ifdef MSM_MASK_TS
         {
-            float dep = acc[QB - 1][NA - 1][3];                   // result of the tile's last MFMA: the move issues once it is complete
+            float dep = acc[NQ - 1][NA - 1][3];                   // result of the tile's last MFMA: the move issues once it is complete
             asm volatile("v_mov_b32 %0, %0" : "+v"(dep));
             MASK_TS(3 + 3 * it)
         }
@@ -656,9 +659,9 @@ __global__ __launch_bounds__(MW * 64) void mask_logits_kernel(const float* __res
                 for (int row = 0; row < 2; ++row)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float v = acc[QB - 1][row][r];
+                        float v = acc[NQ - 1][row][r];
                         v = sum_lane_rows(v);
-                        acc[QB - 1][row][r] = v;
+                        acc[NQ - 1][row][r] = v;
                     }
             }
         }
@@ -1079,16 +1082,28 @@ extern "C" int msm_mask_logits_fwd(const float* mask_embed, const float* mask_fe
     if (mask_out) nc = 1;      // launches that write the logits take 2 x 16 tiles: their float4 stores are accumulator tuples
     const int ctiles = cdiv(W, 16 * nc);
     const int ntiles = n_rowpairs * ctiles;
+    const bool wr = mask_out != nullptr;
+    // Short form: a launch of at most 32 queries that only writes the logits -- the final step on the kept top-K rows --
+    // multiplies QBS = 2 query blocks, not 7 of which 5 are zero rows.  Per-query arithmetic is that of the seven-block kernel
+    // (same MFMA, same k order, bias as the initial accumulator): the rows are bit-equal.  MSM_OPT_MASK_KERNEL = 7 keeps the
+    // seven-block kernel (the comparison the tests make).
+    const bool shortq = wr && pool == 0 && Q <= 16 * QBS && opt(MSM_OPT_MASK_KERNEL) != 7;
+    const int qch = shortq ? 16 * QBS : QCH;
     // persistent-ish grid: enough workgroups per (image, chunk) to cover the chip once
     int wg_per = cdiv(ntiles, MW);
-    const size_t lds = sizeof(float) * ((size_t)QCH * (C + 2) + 2 * QCH);
+    const size_t lds = sizeof(float) * ((size_t)qch * (C + 2) + 2 * qch);
+    // Seven blocks: a tile is C/4*28 (2 x 32) or C/4*14 (2 x 16) MFMAs and the 116 KB chunk allows one workgroup per CU: 256.
+    // Short form: a 2 x 16 tile is C/4*4 MFMAs (C = 64: 2048 cycles, ~1 us) for 128 C bytes of features, so the launch is a
+    // stream over the feature map, not MFMA rounds, and its 9 KB chunk and 76 VGPRs would allow three workgroups per CU.  One per
+    // CU is still the fastest: a wave then walks two or three tiles with the next tile's rows in flight behind the one it
+    // multiplies, and a workgroup stages its chunk once (B = 8, Q = 20 at 120 x 160, 51 MB: 12.5 us with 256 workgroups, 14.6 us
+    // with 512, 15.3 us with one tile per wave -- 600 workgroups; the seven-block kernel takes 22.3 us).
     const int target = cdiv(256, B * qchunks);
     if (wg_per > target) wg_per = max(target, 1);
     dim3 grid(wg_per, qchunks, B), block(MW * 64);
     typedef void (*kern_t)(const float*, const float*, float*, uint8_t*, int32_t*, int, int, int, int, int, int, int, int, int, int, int, int64_t,
                            const float*, int64_t);
     kern_t kern;
-    const bool wr = mask_out != nullptr;
     // Q = 96 + 4 (the 100 queries of every shipped configuration): the last query block on the 4x4x1 MFMA (8 cycles per k-step
     // and image row instead of 32): 10.7 % less matrix time per tile.  Needs 2 x 16 tiles that all take the fast epilogue.
     // MSM_OPT_MASK_KERNEL = 5 selects the kernel without that block (the one tested fallback; round-2 experiments --
@@ -1108,6 +1123,9 @@ extern "C" int msm_mask_logits_fwd(const float* mask_embed, const float* mask_fe
         default: kern = MASK_PICK(8); break;
     }
 #undef MASK_PICK
+    // (short form: the prefetch ring holds a whole tile, four groups of KU k-steps, when C allows: the next tile's rows are
+    // requested group by group while this one is multiplied)
+    if (shortq) kern = (C / (4 * KU)) % 4 == 0 ? (kern_t)mask_logits_kernel<0, true, 1, 4, false, QBS> : (kern_t)mask_logits_kernel<0, true, 1, 2, false, QBS>;
     MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)kern, lds));
     hipLaunchKernelGGL(kern, grid, block, lds, st, mask_embed, mask_feat, mask_out, attn_out, row_any, Q, C, H, W, th, tw,
                        ypar, n_rowpairs, rp_step, rp_first, (int)((int64_t)C * H * W * 4), embed_ld, qbias, qbias_ld);

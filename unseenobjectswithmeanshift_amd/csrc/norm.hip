@@ -265,6 +265,104 @@ __global__ __launch_bounds__(256) void gn_apply_nchw_kernel(const float* __restr
     }
 }
 
+// gn_apply_nchw_kernel for the 64-channel activation of the folded mask step, with the decoder's pooled maps taken from the
+// same pass: a block normalises an 8-row x 16-column tile, so every 2 x 2 centre-tap cell of a reduction by 2, 4 or 8 (rows
+// p ty + p/2 - 1, + 1 and the columns alike; 8 | tile origin) lies inside ONE tile, and the pooled token-major maps of
+// msm_pool_mask_taps are formed from the LDS tile -- the values that go to y, in pool_taps_kernel's summation order -- instead of
+// by a second pass over y.  The launch also clears the row flags that the pooling launch clears.
+// 512 threads: the 34 KB tile allows four workgroups on a CU, which are then its 32 waves (B = 8 at 120 x 160: 17.7 us against
+// 19.2 us with 256 threads; the two launches it replaces take 14.5 + 14.3 us).
+constexpr int GP_C = 64, GP_TH = 8, GP_TW = 16, GP_S = GP_TH * GP_TW + 4, GP_MAXL = 4, GP_T = 512;
+struct GnPoolLevels {
+    int n;
+    int lg[GP_MAXL], th[GP_MAXL], tw[GP_MAXL];      // lg: log2 of the reduction (1, 2, 3)
+    float* out[GP_MAXL];                            // [B][th*tw][64] token-major
+};
+__global__ __launch_bounds__(GP_T) void gn_apply_nchw_pool_kernel(const float* __restrict__ x, const double* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float* __restrict__ y, GnPoolLevels lv, int H, int W, int groups, float eps,
+                                                                 int relu, int32_t* __restrict__ zero_buf, int64_t zero_count) {
+    constexpr int C = GP_C;
+    __shared__ float sc[C], sh[C], mn[C];
+    __shared__ __attribute__((aligned(16))) float tile[C * GP_S];       // [channel][8 x 16 pixels + 4]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.z, r0 = blockIdx.y * GP_TH, c0 = blockIdx.x * GP_TW;
+    const int HW = H * W;
+    if (zero_buf) {
+        const int64_t nthreads = (int64_t)gridDim.x * gridDim.y * gridDim.z * GP_T;
+        for (int64_t i = (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * GP_T + tid; i < zero_count; i += nthreads)
+            zero_buf[i] = 0;
+    }
+    const int cpg = C / groups;
+    if (tid < C) {
+        const int c = tid, g0 = (c / cpg) * cpg;
+        double s = 0.0, q = 0.0;
+        for (int k = 0; k < cpg; ++k) {
+            s += stats[((int64_t)b * C + g0 + k) * 2];
+            q += stats[((int64_t)b * C + g0 + k) * 2 + 1];
+        }
+        const double cnt = (double)cpg * (double)HW;
+        const double mean = s / cnt;
+        double var = q / cnt - mean * mean;
+        if (var < 0.0) var = 0.0;
+        sc[c] = (float)(1.0 / sqrt(var + (double)eps)) * gamma[c];
+        sh[c] = beta[c];
+        mn[c] = (float)mean;
+    }
+    __syncthreads();
+    // (all of a thread's loads are issued before the first is used: the tile is one memory round trip)
+    constexpr int NI = GP_TH * GP_TW * (C / 4) / GP_T;
+    float4 v_[NI];
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const int i = tid + k * GP_T;
+        const int t = i >> 4, c = (i & 15) * 4;                       // t = 16 * (row in tile) + (column in tile)
+        const int p = min(r0 + (t >> 4), H - 1) * W + min(c0 + (t & 15), W - 1);
+        v_[k] = *reinterpret_cast<const float4*>(x + ((int64_t)b * HW + p) * C + c);
+    }
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const int i = tid + k * GP_T;
+        const int t = i >> 4, c = (i & 15) * 4;
+        float4 v = v_[k];
+        v.x = (v.x - mn[c]) * sc[c] + sh[c];
+        v.y = (v.y - mn[c + 1]) * sc[c + 1] + sh[c + 1];
+        v.z = (v.z - mn[c + 2]) * sc[c + 2] + sh[c + 2];
+        v.w = (v.w - mn[c + 3]) * sc[c + 3] + sh[c + 3];
+        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        tile[(c + 0) * GP_S + t] = v.x;
+        tile[(c + 1) * GP_S + t] = v.y;
+        tile[(c + 2) * GP_S + t] = v.z;
+        tile[(c + 3) * GP_S + t] = v.w;
+    }
+    __syncthreads();
+    for (int i = tid; i < C * GP_TH * (GP_TW / 4); i += GP_T) {
+        const int c = i >> 5, ry = (i >> 2) & 7, x4 = (i & 3) * 4;
+        if (r0 + ry < H && c0 + x4 < W)          // W % 4 == 0: a float4 is inside or outside as a whole
+            *reinterpret_cast<float4*>(y + (((int64_t)b * C + c) * H + r0 + ry) * W + c0 + x4) =
+                *reinterpret_cast<const float4*>(tile + c * GP_S + ry * GP_TW + x4);
+    }
+    for (int l = 0; l < lv.n; ++l) {
+        const int lg = lv.lg[l], pp = 1 << lg, th = lv.th[l], tw = lv.tw[l];
+        const int lx = 4 - lg;                                          // log2 of the targets per tile row (GP_TW >> lg)
+        const int nt = (GP_TH >> lg) << lx;                            // targets of this level in a tile: 32, 8, 2
+        float* ob = lv.out[l] + (int64_t)b * th * tw * C;
+        for (int i = tid; i < nt * (C / 4); i += GP_T) {
+            const int tt = i >> 4, c4 = (i & 15) * 4;
+            const int jy = tt >> lx, jx = tt & ((1 << lx) - 1);
+            const int ty = (r0 >> lg) + jy, tx = (c0 >> lg) + jx;
+            if (ty >= th || tx >= tw) continue;                          // cells beyond the map (partial tiles)
+            const float* q = tile + c4 * GP_S + ((jy << lg) + pp / 2 - 1) * GP_TW + (jx << lg) + pp / 2 - 1;
+            float4 r;
+            r.x = 0.25f * ((q[0] + q[1]) + (q[GP_TW] + q[GP_TW + 1]));
+            r.y = 0.25f * ((q[GP_S] + q[GP_S + 1]) + (q[GP_S + GP_TW] + q[GP_S + GP_TW + 1]));
+            r.z = 0.25f * ((q[2 * GP_S] + q[2 * GP_S + 1]) + (q[2 * GP_S + GP_TW] + q[2 * GP_S + GP_TW + 1]));
+            r.w = 0.25f * ((q[3 * GP_S] + q[3 * GP_S + 1]) + (q[3 * GP_S + GP_TW] + q[3 * GP_S + GP_TW + 1]));
+            *reinterpret_cast<float4*>(ob + ((int64_t)ty * tw + tx) * C + c4) = r;
+        }
+    }
+}
+
 // ---- position encoding -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pos_embed_kernel(float* __restrict__ out, int H, int W, int npf, int64_t s_c,
                                                         int64_t s_p, const float* __restrict__ add_c,
@@ -494,6 +592,41 @@ extern "C" int msm_groupnorm_apply_nchw_f32(const float* x, const double* stats,
     dim3 grid(cdiv(HW, 64), B), block(256);
     hipLaunchKernelGGL(gn_apply_nchw_kernel, grid, block, lds, (hipStream_t)stream, x, stats, gamma, beta, y, HW, C, groups, eps, relu);
     MSM_CHECK_LAUNCH("msm_groupnorm_apply_nchw_f32");
+    return MSM_OK;
+}
+
+extern "C" int msm_groupnorm_nchw_pool_f32(const float* x, const double* stats, const float* gamma, const float* beta, float* y, int B,
+                                          int H, int W, int C, int groups, float eps, int relu, int n_levels, const int32_t* th,
+                                          const int32_t* tw, float* const* out, int32_t* zero_buf, int64_t zero_count, void* stream) {
+    MSM_REQUIRE(x && stats && gamma && beta && y && x != y, "msm_groupnorm_nchw_pool_f32: null or aliased pointer");
+    MSM_REQUIRE(B > 0 && H > 1 && W > 1 && W % 4 == 0, "msm_groupnorm_nchw_pool_f32: %dx%d: W must be a multiple of 4", H, W);
+    MSM_REQUIRE(C == GP_C && groups > 0 && C % groups == 0, "msm_groupnorm_nchw_pool_f32: C=%d groups=%d (the 64-channel activation)", C, groups);
+    MSM_REQUIRE(((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0, "msm_groupnorm_nchw_pool_f32: pointers must be 16-byte aligned");
+    MSM_REQUIRE(!zero_buf || zero_count > 0, "msm_groupnorm_nchw_pool_f32: zero_buf needs a positive count");
+    MSM_REQUIRE(th && tw && out && n_levels >= 1 && n_levels <= GP_MAXL, "msm_groupnorm_nchw_pool_f32: bad arguments (1..%d levels)", GP_MAXL);
+    if (opt(MSM_OPT_GN_POOL) == 0) {      // the two launches this one replaces (the comparison the tests make)
+        if (int rc = msm_groupnorm_apply_nchw_f32(x, stats, gamma, beta, y, B, H * W, C, groups, eps, relu, stream)) return rc;
+        return msm_pool_mask_taps(y, B, H, W, n_levels, th, tw, out, zero_buf, zero_count, stream);
+    }
+    GnPoolLevels lv;
+    lv.n = n_levels;
+    for (int l = 0; l < GP_MAXL; ++l) {
+        if (l < n_levels) {
+            MSM_REQUIRE(out[l] && th[l] > 0 && tw[l] > 0 && H % th[l] == 0 && W % tw[l] == 0 && H / th[l] == W / tw[l],
+                        "msm_groupnorm_nchw_pool_f32: level %d (%dx%d) is not an integer reduction of %dx%d", l, th[l], tw[l], H, W);
+            const int p = H / th[l];
+            MSM_REQUIRE(p == 2 || p == 4 || p == 8, "msm_groupnorm_nchw_pool_f32: ratio %d not in {2, 4, 8}", p);
+            MSM_REQUIRE((((uintptr_t)out[l]) & 15) == 0, "msm_groupnorm_nchw_pool_f32: misaligned output");
+            lv.lg[l] = p == 2 ? 1 : (p == 4 ? 2 : 3); lv.th[l] = th[l]; lv.tw[l] = tw[l]; lv.out[l] = out[l];
+        } else {
+            lv.lg[l] = 1; lv.th[l] = lv.tw[l] = 0; lv.out[l] = nullptr;
+        }
+    }
+    dim3 grid(cdiv(W, GP_TW), cdiv(H, GP_TH), B), block(GP_T);
+    MSM_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "msm_groupnorm_nchw_pool_f32: %dx%d x %d images exceeds the grid", H, W, B);
+    hipLaunchKernelGGL(gn_apply_nchw_pool_kernel, grid, block, 0, (hipStream_t)stream, x, stats, gamma, beta, y, lv, H, W, groups, eps, relu,
+                       zero_buf, zero_count);
+    MSM_CHECK_LAUNCH("msm_groupnorm_nchw_pool_f32");
     return MSM_OK;
 }
 

@@ -173,6 +173,9 @@ class MeanShiftMaskFormerHead(PlanAttributes, nn.Module):
         kw = {}
         if getattr(self.predictor, "folded_mask_features", False) and _accepts(self.pixel_decoder.forward_features, "folded"):
             kw["folded"] = True
+            # ... and says which pooled maps of the activation it will want: they leave the launch that writes the activation
+            if hasattr(self.predictor, "pool_request") and _accepts(self.pixel_decoder.forward_features, "pool_request"):
+                kw["pool_request"] = self.predictor.pool_request
         mask_features, _, multi_scale_features = self.pixel_decoder.forward_features(features, **kw)
         if final_topk and _accepts(self.predictor.forward, "final_topk"):
             predictions = self.predictor(multi_scale_features, mask_features, mask, final_topk=final_topk)

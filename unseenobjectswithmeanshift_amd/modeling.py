@@ -83,10 +83,15 @@ class FoldedMaskFeatures:
     so a decoder that understands this object contracts the 64-channel ``act`` with the folded embedding e W (64 columns)
     plus a per-query constant e.b -- a quarter of the FLOPs and of the bytes of the mask step, and the 1x1 convolution that
     would write the (B, 256, H, W) tensor is never run.  ``tensor()`` materialises the literal mask_features for any other
-    consumer (same kernels as the unfolded pixel decoder)."""
+    consumer (same kernels as the unfolded pixel decoder).
 
-    def __init__(self, act, weight, bias, materialize):
+    ``pooled`` (optional): (sizes, maps, flags) -- the centre-tap means of ``act`` at the level sizes the decoder asked for
+    (``MeanShiftTransformerDecoder.pool_request``) and its cleared (B, rows) int32 row flags, written by the launch that
+    wrote ``act`` (ops.groupnorm_nchw_pool); a decoder that finds what it wants there does not pool ``act`` again."""
+
+    def __init__(self, act, weight, bias, materialize, pooled=None):
         self.act, self.weight, self.bias = act, weight, bias
+        self.pooled = pooled
         self._materialize = materialize
         self._tensor = None
 
@@ -512,7 +517,8 @@ class MeanShiftTransformerDecoder(PlanAttributes, nn.Module):
     def _poolable_sizes(act, sizes):
         """Level sizes that are integer reductions (2, 4, 8) of the mask-feature map: their attention masks can be computed at key
         resolution (csrc/attn_mask.hip)."""
-        Hm, Wm = int(act.shape[2]), int(act.shape[3])
+        shape = getattr(act, "shape", act)
+        Hm, Wm = int(shape[2]), int(shape[3])
         out = []
         for (th, tw) in sizes:
             if (int(th), int(tw)) not in out and Hm % th == 0 and Wm % tw == 0 and Hm // th == Wm // tw and Hm // th in (2, 4, 8):
@@ -523,6 +529,31 @@ class MeanShiftTransformerDecoder(PlanAttributes, nn.Module):
         """Whether the 16-bit plan's K rows are IEEE-half bit patterns (kv_format 2): ONE decision for the projection that writes them and
         the attention kernels that read them.  The half-key form exists for 2E = 512 only; any other width keeps bf16 keys."""
         return self.attention_dtype == "bf16" and self.attention_keys == "f16" and 2 * self.query_feat.weight.shape[1] == 512
+
+    def _pool_plan(self, act_shape, sizes, Qn):
+        """What _forward_fused pools the (B, 64, H, W) activation of the folded mask features to: (level sizes, row flags cleared
+        per image, whether the heads launches derive the masks themselves), or None when it computes its attention masks at full
+        resolution."""
+        full, L = self.aux_outputs, self.num_layers
+        if not (self.pooled_attention_masks and (not full or self.pooled_attention_masks == "always") and int(act_shape[1]) == 64 and L > 0):
+            return None
+        want_sizes = self._poolable_sizes(act_shape, sizes)
+        if not want_sizes:
+            return None
+        # (the pooling launch also clears the row flags of prediction 0's attention-mask step)
+        # (... and, for the fused heads + mask launches, of every later prediction's: one (L + 1, B, Q) buffer)
+        fuse_masks = bool(self.fused_head_masks) and self.tails_dtype in ("bf16", "f16") and not self._tails_hl_for("heads") and not full \
+            and self.lp_pooled_masks != "x3"          # (the epilogue form has the fp32 and the single-half contraction)
+        return want_sizes, Qn * (L + 1 if fuse_masks else 1), fuse_masks
+
+    def pool_request(self, act_shape, sizes):
+        """For the pixel decoder (forward_features(pool_request=...)): the (level sizes, flag rows per image) this decoder will pool
+        a FoldedMaskFeatures activation of shape ``act_shape`` to, given the multi-scale level ``sizes`` -- or None.  The launch that
+        writes the activation can then write the pooled maps too (FoldedMaskFeatures.pooled)."""
+        if not (self.folded_mask_features and self.fused_tails and self.fold_kv and int(act_shape[1]) < self.query_feat.weight.shape[1]):
+            return None
+        plan = self._pool_plan(act_shape, [(int(h), int(w)) for h, w in sizes], int(self.query_feat.weight.shape[0]))
+        return None if plan is None else plan[:2]
 
     def _kv_one(self, x, w, cc):
         """One layer's folded K/V projection when the layers' K/V are not all resident at once (the 307 200-key UCN path): the
@@ -598,20 +629,20 @@ class MeanShiftTransformerDecoder(PlanAttributes, nn.Module):
             # the heads kernel emits [e Wm | e.bm | 0...] instead of e; the mask step runs on the 64-channel activation
             wf, bf, ncol = self._folded_head(mask_features)
             mlp[-1] = (wf, bf)
+            handed = mask_features.pooled
             mask_features = mask_features.act
-            if self.pooled_attention_masks and (not full or self.pooled_attention_masks == "always") and ncol == 64 and mask_features.shape[1] == 64:
-                # attention masks at key resolution: pool the activation once to every level size that is an integer reduction
-                want_sizes = self._poolable_sizes(mask_features, sizes)
-                if want_sizes and L > 0:
-                    # (the pooling launch also clears the row flags of prediction 0's attention-mask step)
-                    # (... and, for the fused heads + mask launches, of every later prediction's: one (L + 1, B, Q) buffer)
-                    fuse_masks = bool(self.fused_head_masks) and self.tails_dtype in ("bf16", "f16") and not self._tails_hl_for("heads") and not full \
-                        and self.lp_pooled_masks != "x3"          # (the epilogue form has the fp32 and the single-half contraction)
-                    Bq, Qn = int(out.shape[0]), int(out.shape[1])
-                    outs, flags = ops.pool_mask_taps(mask_features, want_sizes, zero_rows=Qn * (L + 1 if fuse_masks else 1))
-                    ra_all = flags.view(-1)[:Bq * Qn * (L + 1 if fuse_masks else 1)].view(-1, Bq, Qn)
-                    ra0 = ra_all[0]
-                    pooled = dict(zip(want_sizes, outs))
+            Bq, Qn = int(out.shape[0]), int(out.shape[1])
+            # attention masks at key resolution: the activation pooled once to every level size that is an integer reduction
+            plan = self._pool_plan(mask_features.shape, sizes, Qn) if ncol == 64 else None
+            if plan is not None:
+                want_sizes, rows, fuse_masks = plan
+                if handed is not None and list(handed[0]) == want_sizes and handed[2] is not None and tuple(handed[2].shape) == (Bq, rows):
+                    outs, flags = handed[1], handed[2]          # written and cleared by the launch that wrote the activation
+                else:
+                    outs, flags = ops.pool_mask_taps(mask_features, want_sizes, zero_rows=rows)
+                ra_all = flags.view(-1)[:Bq * rows].view(-1, Bq, Qn)
+                ra0 = ra_all[0]
+                pooled = dict(zip(want_sizes, outs))
         dn = self.decoder_norm
         pred_cls, pred_mask = [], []
         topk_out = []
@@ -1368,9 +1399,9 @@ class MSDeformAttnPixelDecoder(PlanAttributes, nn.Module):
                 src = layer.forward_tokens(src, lvl_pos, ss, starts)
         return src, shapes, fpn_stats
 
-    def _fpn_mask_features(self, features, up_tok, up_hw, fpn_stats, folded=False):
+    def _fpn_mask_features(self, features, up_tok, up_hw, fpn_stats, folded=False, pool_request=None):
         """The one FPN level on res2 and the mask_features convolution (MSD:343-358); up_tok: the finest encoder level as a
-        token-range view of the encoder's buffer."""
+        token-range view of the encoder's buffer.  pool_request (folded form): activation shape -> None or (pooled sizes, flag rows)."""
         C = self.conv_dim
         B = up_tok.shape[0]
         # one FPN level on the highest-resolution backbone feature (MSD:343-351)
@@ -1412,6 +1443,13 @@ class MSDeformAttnPixelDecoder(PlanAttributes, nn.Module):
                                          eps=self.layer_1.norm.eps), wm, self.mask_features.bias).view(B, self.mask_dim, H, W)
             if folded:
                 # hand over the factored form: the 64-channel activation as NCHW planes + the 1x1 weight (FoldedMaskFeatures)
+                req = pool_request((B, C, H, W)) if (pool_request is not None and W % 4 == 0) else None
+                if req:
+                    # ... and, from the same launch, the pooled maps and cleared row flags the decoder said it will want
+                    want_sizes, rows = req
+                    act, outs, flags = ops.groupnorm_nchw_pool(y, y_stats, self.layer_1.norm.weight, self.layer_1.norm.bias, H, W, want_sizes,
+                                                               groups=32, eps=self.layer_1.norm.eps, relu=True, zero_rows=rows)
+                    return FoldedMaskFeatures(act, wm, self.mask_features.bias, literal, pooled=(list(want_sizes), outs, flags))
                 act = ops.groupnorm_nchw(y, y_stats, self.layer_1.norm.weight, self.layer_1.norm.bias, groups=32,
                                          eps=self.layer_1.norm.eps, relu=True).view(B, C, H, W)
                 return FoldedMaskFeatures(act, wm, self.mask_features.bias, literal)
@@ -1423,10 +1461,11 @@ class MSDeformAttnPixelDecoder(PlanAttributes, nn.Module):
         return mask_features
 
     @torch.no_grad()
-    def forward_features(self, features, folded=False):
+    def forward_features(self, features, folded=False, pool_request=None):
         """Returns (mask_features, encoder level 0, multi-scale features) like the reference.  ``folded=True`` (asked for by a
         head whose predictor understands it) returns mask_features as FoldedMaskFeatures instead of a (B, mask_dim, H, W)
-        tensor."""
+        tensor.  ``pool_request`` (with ``folded``): the predictor's ``pool_request(act_shape, level_sizes)``; what it asks for is
+        written with the activation (FoldedMaskFeatures.pooled)."""
         C = self.conv_dim
         src, shapes, fpn_stats = self._encode(features)
         B = src.shape[0]
@@ -1437,5 +1476,8 @@ class MSDeformAttnPixelDecoder(PlanAttributes, nn.Module):
             out.append(src[:, o:o + h * w].view(B, h, w, C).permute(0, 3, 1, 2))
             o += h * w
         up_tok = src[:, o - shapes[-1][0] * shapes[-1][1]:]                       # finest level, source of the FPN upsample (a view)
-        mask_features = self._fpn_mask_features(features, up_tok, shapes[-1], fpn_stats, folded)
+        want = None
+        if folded and pool_request is not None:
+            want = lambda act_shape: pool_request(act_shape, shapes[:self.maskformer_num_feature_levels])
+        mask_features = self._fpn_mask_features(features, up_tok, shapes[-1], fpn_stats, folded, want)
         return mask_features, out[0], out[:self.maskformer_num_feature_levels]

@@ -344,6 +344,28 @@ def groupnorm_nchw(x, stats, gamma, beta, *, groups=32, eps=1e-5, relu=False):
     return y
 
 
+def groupnorm_nchw_pool(x, stats, gamma, beta, H, W, sizes, *, groups=32, eps=1e-5, relu=False, zero_rows=0):
+    """groupnorm_nchw of a 64-channel token map x (B, H*W, 64) and pool_mask_taps of the result in one launch
+    (msm_groupnorm_nchw_pool_f32; W % 4 == 0): -> (act (B, 64, H, W), [pooled (B, th*tw, 64) per (th, tw) of ``sizes``],
+    flags).  ``flags``: a cleared (B, zero_rows) int32 buffer, None when zero_rows == 0.  Bit-equal to the two launches."""
+    _c(x, "x"), _c(stats, "stats", torch.float64), _c(gamma, "gamma"), _c(beta, "beta")
+    B, HW, C = x.shape
+    if C != 64 or HW != H * W or not 1 <= len(sizes) <= 4:
+        raise RuntimeError("groupnorm_nchw_pool needs a (B, H*W, 64) token map and 1..4 target sizes")
+    y = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32)
+    outs = [torch.empty((B, int(th) * int(tw), 64), device=x.device, dtype=torch.float32) for th, tw in sizes]
+    n = len(sizes)
+    ths = (ctypes.c_int32 * n)(*[int(s[0]) for s in sizes])
+    tws = (ctypes.c_int32 * n)(*[int(s[1]) for s in sizes])
+    ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    flags = torch.empty((B, int(zero_rows)), device=x.device, dtype=torch.int32) if zero_rows else None
+    rc = lib().msm_groupnorm_nchw_pool_f32(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), B, int(H), int(W), C, int(groups), float(eps),
+                                           1 if relu else 0, n, ctypes.cast(ths, ctypes.c_void_p), ctypes.cast(tws, ctypes.c_void_p),
+                                           ctypes.cast(ptrs, ctypes.c_void_p), _p(flags), B * int(zero_rows), _stream())
+    check(rc, "msm_groupnorm_nchw_pool_f32")
+    return y, outs, flags
+
+
 def groupnorm_stats(x, stats=None):
     """Per-(image, channel) double (sum, sum of squares) of a token map x (B, HW, C) -> (B, C, 2) float64.  ``stats``: a
     ZEROED (B, C, 2) float64 tensor to accumulate into (then no fill launch is issued)."""
