@@ -66,7 +66,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 29   /* 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 30   /* 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -593,24 +593,35 @@ int msm_hypersphere_attn_bwd(const float* q, const float* k, const float* v, con
 /* ---------------------------------------------------------------------------------------------
  * Classic vMF mean shift over unit embeddings X [n][d] (d == 64), cosine metric.
  * ------------------------------------------------------------------------------------------- */
-/* Farthest-point seeding (MS:155-187): indices[0] = first_index, then S-1 x { nearest =
- * min(nearest, 0.5*(1 - X.s)); next = first argmax }.  seeds_out [S][d], indices_out int64 [S].
- * workspace floats >= msm_ms_seed_workspace(n).
- * Maps of up to 393 216 rows take ONE persistent launch whose workgroups meet at a grid barrier after every step; that
- * needs all of them co-resident.  When other work holds CUs for too long the kernel gives up at a bounded wait and
- * writes -1 to every index (the seeds are then undefined): the caller re-issues the call with flags bit 0 set, which
- * takes the one-launch-per-step path (identical results).  flags bit 0: stepwise path. */
+/* Every fp32 stage takes M maps of one size per call, X [M][n][64] contiguous (M <= 65535): the second stage of the two-stage
+ * clustering (lib/fcn/test_dataset.py:232-267) clusters one small map per object crop (224 x 224: n = 50 176), many per frame, and
+ * one map at a time would leave most of the chip idle and pay every launch and every seeding exchange per map.  A map's arithmetic,
+ * per-map grid and summation order do not depend on M: each output equals, bit for bit, what a call with that map alone gives. */
+/* Farthest-point seeding (MS:155-187): indices[0] = first index, then S-1 x { nearest =
+ * min(nearest, 0.5*(1 - X.s)); next = first argmax }.  seeds_out [M][S][d], indices_out int64 [M][S].
+ * First indices: first_indices int64 [M] on the DEVICE, each in [0, n) (values outside are clamped into the map), or null with
+ * the host value first_index in [0, n), which is allowed for M == 1 only.
+ * workspace floats >= msm_ms_seed_workspace(M, n), 8-byte aligned.
+ * Maps of 4096 .. 393 216 rows take persistent launches whose workgroups exchange their candidates after every step; that needs
+ * all of them co-resident.  One map is held by cdiv(n, 512 ng) workgroups, ng = cdiv(n, 131072); of several maps each is held by
+ * G = cdiv(n, 1536) workgroups, a launch carries floor(min(CUs, 256) / G) maps (grid (G, maps): a map's workgroups are those of one
+ * blockIdx.y) and the call issues as many launches as M needs.
+ * When other work holds CUs for too long a map's workgroups give up at a bounded wait and write -1 to every index of THAT map (its
+ * seeds are then undefined): the caller re-issues those maps with MSM_MS_SEED_STEPWISE, which takes the one-launch-per-step path
+ * (no waiting between workgroups, identical indices).  With MSM_MS_SEED_TEST_GIVE_UP, map m starts with its give-up flag raised
+ * when bit (m mod 64) of test_give_up_mask is set (tests). */
 #define MSM_MS_SEED_STEPWISE 1
-#define MSM_MS_SEED_TEST_GIVE_UP 2   /* tests: the persistent kernel starts with its give-up flag raised */
-int64_t msm_ms_seed_workspace(int n);
-int msm_ms_select_seeds(const float* X, int n, int d, int num_seeds, int64_t first_index,
-                        float* seeds_out, int64_t* indices_out,
-                        float* workspace, int64_t workspace_elems, int flags, void* stream);
-/* iters x { Z = normalize( exp(kappa * Z X^T) X ) } (MS:90-107); Z [S][d] updated in place. */
+#define MSM_MS_SEED_TEST_GIVE_UP 2   /* tests: maps start with their give-up flag raised (test_give_up_mask) */
+int64_t msm_ms_seed_workspace(int M, int n);
+int msm_ms_select_seeds(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices, int64_t first_index,
+                        float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags,
+                        uint64_t test_give_up_mask, void* stream);
+/* iters x { Z = normalize( exp(kappa * Z X^T) X ) } (MS:90-107); Z [M][S][d] updated in place.  msm_ms_hill_climb_workspace is the
+ * partial sums of ONE map: workspace floats >= M * msm_ms_hill_climb_workspace(n, S). */
 int64_t msm_ms_hill_climb_workspace(int n, int S);
-int msm_ms_hill_climb(const float* X, int n, int d, float* Z, int S, float kappa, int iters,
+int msm_ms_hill_climb(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters,
                       float* workspace, int64_t workspace_elems, void* stream);
-/* The same iteration with every fp32 product carried out as six bf16 MFMAs on exact three-term splits of both operands (X,
+/* The same iteration for one map (X [n][d], Z [S][d]) with every fp32 product carried out as six bf16 MFMAs on exact three-term splits of both operands (X,
  * Z and the exp() weights): fp32-accurate results -- the error against float64 stays within 1.5x of the fp32 MFMA kernel's --
  * at 0.375 of its matrix time.  X is split once per call into three bf16 planes kept in the workspace (6 bytes per element),
  * which is therefore larger: msm_ms_hill_climb_split_workspace floats, 16-byte aligned like X and Z.  Opt-in (the host passes
@@ -624,7 +635,7 @@ int msm_ms_hill_climb_split(const float* X, int n, int d, float* Z, int S, float
  * three in the hill climb (MS:79-109) with single bf16 products except the seeds (h + l terms).  Distances are those of the rounded
  * points: seeds and labels equal the fp32 results up to which member of a cluster is picked / a permutation of the labels
  * (SURVEY 8c); the fp32 and f32_split entry points stay exact.
- * msm_ms_select_seeds_bf16: workspace as msm_ms_select_seeds (msm_ms_seed_workspace(n) floats); seeds_out are rows of the fp32 X
+ * One map per call.  msm_ms_select_seeds_bf16: workspace as msm_ms_select_seeds (msm_ms_seed_workspace(1, n) floats); seeds_out are rows of the fp32 X
  * (MS:186-189 returns X[selected]); n >= 16.  flags as msm_ms_select_seeds: maps of >= 65536 rows take ONE persistent launch that
  * keeps 917 504 rows of the copy on chip (VGPRs + LDS) and streams the rest per step; it gives up (indices -1) under the same
  * co-residency condition, and MSM_MS_SEED_STEPWISE selects the one-launch-per-step kernel, whose indices are bit-identical.  msm_ms_hill_climb_bf16: workspace msm_ms_hill_climb_workspace(n, S) floats. */
@@ -634,50 +645,22 @@ int msm_ms_select_seeds_bf16(const void* Xb, const float* X, int n, int d, int n
                              int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags, void* stream);
 int msm_ms_hill_climb_bf16(const void* Xb, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
                            int64_t workspace_elems, void* stream);
-/* closest = first argmin_s 0.5*(1 - X.Z_s); labels_out[i] = seed_labels[closest] (int64);
- * counts int64 [num_labels] histogram of labels_out (zeroed here) (MS:206-221). */
-int msm_ms_assign(const float* X, int n, int d, const float* Z, int S, const int64_t* seed_labels,
+/* closest = first argmin_s 0.5*(1 - X.Z_s); labels_out[m][i] = seed_labels[m][closest] (int64 [M][n]; Z [M][S][64],
+ * seed_labels int64 [M][S]); counts int64 [M][num_labels] histogram of labels_out (zeroed here) (MS:206-221). */
+int msm_ms_assign(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
                   int64_t* labels_out, int64_t* counts, int num_labels, void* stream);
 /* connected_components of the converged seeds (lib/utils/mean_shift.py:41-76: sequential, order dependent) on the device:
- * Z [S][64] unit rows, S <= 304; seed_labels int64 [S] (labels in order of creation; a later step may overwrite every seed
- * of an earlier label, as in the reference); num_labels int32 [2] = {labels that survive = len(unique(seed_labels)), labels
- * created}; one wave, no host involvement. */
-int msm_ms_connected_components(const float* Z, int S, int d, float epsilon, int64_t* seed_labels, int32_t* num_labels,
+ * Z [M][S][64] unit rows, S <= 304; seed_labels int64 [M][S] (labels in order of creation; a later step may overwrite every seed
+ * of an earlier label, as in the reference); num_labels int32 [M][2] = {labels that survive = len(unique(seed_labels)), labels
+ * created}; one wave per map, no host involvement. */
+int msm_ms_connected_components(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels, int32_t* num_labels,
                                 void* stream);
-/* swap label 0 with the first-argmax label of counts[0 .. num) (MS:211-227); labels int64 [n] in place.  num = min(num_labels,
- * *num_alive) when num_alive (device, e.g. num_labels[0] of msm_ms_connected_components) is given: the reference counts the
- * labels 0 .. len(unique(seed_labels)) - 1 only, which differs from "every label" once a label has vanished. */
-int msm_ms_relabel_largest_zero(int64_t* labels, int n, const int64_t* counts, int num_labels, const int32_t* num_alive,
+/* swap label 0 with the first-argmax label of counts[0 .. num) (MS:211-227); labels int64 [M][n] in place, counts [M][num_labels].
+ * num = min(num_labels, num_alive[m][0]) when num_alive (device int32 [M][2], e.g. num_labels of msm_ms_connected_components; only
+ * element 0 of a map's pair is read) is given: the reference counts the labels 0 .. len(unique(seed_labels)) - 1 only, which
+ * differs from "every label" once a label has vanished. */
+int msm_ms_relabel_largest_zero(int64_t* labels, int M, int n, const int64_t* counts, int num_labels, const int32_t* num_alive,
                                 void* stream);
-/* ---- M maps of one size per call (exact fp32 plan only) ----
- * The second stage of the two-stage clustering (lib/fcn/test_dataset.py:232-267) clusters one small map per object crop
- * (224 x 224: n = 50 176), many per frame; a single-map call leaves most of the chip idle for such a map and pays every launch
- * and every seeding exchange per map.  These entry points take X [M][n][64] contiguous and give every stage a map dimension
- * without changing one map's arithmetic: each output equals, bit for bit, what the single-map entry point gives for that map.
- * msm_ms_select_seeds_batched: first_indices int64 [M] on the DEVICE, each in [0, n) (values outside are clamped into the map);
- *   seeds_out [M][S][64], indices_out int64 [M][S]; workspace floats >= msm_ms_seed_batched_workspace(M, n), 8-byte aligned.
- *   Maps of 4096 .. 393 216 rows take grouped persistent launches: a map is held by G = cdiv(n, 1536) workgroups, a launch
- *   carries floor(min(CUs, 256) / G) maps and the call issues as many launches as M needs.  A group that loses co-residency gives
- *   up at a bounded wait and reports -1 for ITS map's indices only; the caller re-issues those maps with MSM_MS_SEED_STEPWISE
- *   (one launch per step for all maps, no waiting between workgroups, identical indices).  With MSM_MS_SEED_TEST_GIVE_UP, map m
- *   starts with its give-up flag raised when bit (m mod 64) of test_give_up_mask is set (tests).
- * msm_ms_hill_climb_batched: Z [M][S][64] in place; workspace floats >= msm_ms_hill_climb_batched_workspace(M, n, S).
- * msm_ms_connected_components_batched: one wave per map; seed_labels int64 [M][S], num_labels int32 [M][2].
- * msm_ms_assign_batched: seed_labels [M][S] -> labels_out int64 [M][n], counts int64 [M][num_labels] (zeroed here).
- * msm_ms_relabel_largest_zero_batched: labels [M][n] in place, counts [M][num_labels], num_alive int32 [M][2] or null. */
-int64_t msm_ms_seed_batched_workspace(int M, int n);
-int msm_ms_select_seeds_batched(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices,
-                                float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags,
-                                uint64_t test_give_up_mask, void* stream);
-int64_t msm_ms_hill_climb_batched_workspace(int M, int n, int S);
-int msm_ms_hill_climb_batched(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
-                              int64_t workspace_elems, void* stream);
-int msm_ms_assign_batched(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
-                          int64_t* labels_out, int64_t* counts, int num_labels, void* stream);
-int msm_ms_connected_components_batched(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
-                                        int32_t* num_labels, void* stream);
-int msm_ms_relabel_largest_zero_batched(int64_t* labels, int M, int n, const int64_t* counts, int num_labels,
-                                        const int32_t* num_alive, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Instance post-processing for one batch (pretrained_meanshiftformer_model.py:337-343,461-497):

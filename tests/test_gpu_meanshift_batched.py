@@ -1,7 +1,9 @@
 """The classic clustering for M maps of one size per call (ops.ms_*_batched, mean_shift.mean_shift_smart_init_batched, the
 batched route of mean_shift.clustering_features) against the single-map ops called in a loop with the same first indices.
-The batched kernels give every stage a map dimension without touching one map's arithmetic, so every comparison here is
-torch.equal, never a tolerance.  Needs a real MI355X (pytest -m gpu)."""
+The single-map ops are the M = 1 case of the same kernels and entry points, so what these tests prove is that a map's result
+does not depend on M, on its neighbours or on how maps are spread over launches -- every comparison is torch.equal, never a
+tolerance.  That one map is computed correctly is checked against references in tests/test_gpu_ops.py and test_gpu_modules.py.
+Needs a real MI355X (pytest -m gpu)."""
 import numpy as np
 import pytest
 import torch
@@ -51,8 +53,10 @@ def loop_seeds(M, n, S):
 
 
 # (M, n, S): smallest persistent map | n no multiple of 16, 4 workgroups per map | 224 x 224 crops: 33 workgroups per map, seven
-# maps per launch -> two launches (7 + 2) | 98 workgroups per map, two maps per launch
-@pytest.mark.parametrize("M,n,S", [(2, 4096, 3), (9, 5003, 40), (9, 50176, 100), (3, 150000, 40)])
+# maps per launch -> two launches (7 + 2) | 98 workgroups per map, two maps per launch | one map: the M = 1 launch policy (8
+# workgroups of one tile) with a device first index against the same entry point with a host scalar; with one map the
+# neighbour half of the give-up check compares empty tensors, only the -1 half says anything
+@pytest.mark.parametrize("M,n,S", [(2, 4096, 3), (9, 5003, 40), (9, 50176, 100), (3, 150000, 40), (1, 4096, 3)])
 def test_seeding_grouped(M, n, S):
     X, first = maps(M, n)
     seeds_l, sel_l = loop_seeds(M, n, S)
@@ -68,8 +72,8 @@ def test_seeding_grouped(M, n, S):
     assert torch.equal(sel_d, sel_l) and torch.equal(seeds_d, seeds_l)
 
 
-# (3, 15, 5): fewer rows than the butterfly's 16
-@pytest.mark.parametrize("M,n,S", [(3, 15, 5), (3, 1000, 20), (9, 5003, 40)])
+# (3, 15, 5): fewer rows than the butterfly's 16; (1, 15, 5): the same kernel with a host scalar as first index on the partner's side
+@pytest.mark.parametrize("M,n,S", [(3, 15, 5), (3, 1000, 20), (9, 5003, 40), (1, 15, 5)])
 def test_seeding_stepwise(M, n, S, lib_option):
     X, first = maps(M, n)
     seeds_l, sel_l = loop_seeds(M, n, S)
@@ -106,8 +110,8 @@ def test_give_up_is_per_map_and_falls_back():
     assert torch.equal(sel, sel_c)
 
 
-# the last case has more than 8 x 16 = 128 seeds: the seed-block chunking of a launch is walked
-@pytest.mark.parametrize("M,n,S,iters", [(3, 1000, 20, 2), (2, 50176, 100, 10), (5, 5003, 130, 3)])
+# 130 seeds are more than 8 x 16 = 128: nine seed blocks, two chunks per iteration; the M = 1 cases walk them with one map's strides
+@pytest.mark.parametrize("M,n,S,iters", [(3, 1000, 20, 2), (2, 50176, 100, 10), (5, 5003, 130, 3), (1, 1000, 20, 2), (1, 5003, 130, 1)])
 def test_hill_climb(M, n, S, iters):
     X, _ = maps(M, n)
     Z0 = X[:, :: n // S][:, :S].contiguous()
@@ -141,6 +145,8 @@ def test_merge_assign_relabel():
     ops().ms_relabel_largest_zero_batched(again, counts)
     for m in range(M):
         assert torch.equal(again[m], ops().ms_relabel_largest_zero(before[m].clone(), counts[m]))
+    # one map may pass the count alone (mean_shift._components_with_count does): element 0 of a map's pair is all that is read
+    assert torch.equal(ops().ms_relabel_largest_zero(before[0].clone(), counts[0], num[0, :1]), labels[0])
 
 
 def _features(M, H, W):

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmsm_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msm_hip.h")
 
 _lib = None
-ABI_VERSION = 29     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
+ABI_VERSION = 30     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
 
 c_f = ctypes.c_void_p      # float* (device)
 c_p = ctypes.c_void_p
@@ -115,26 +115,19 @@ _SIGNATURES = {
                              [c_p, c_i, c_i, c_i, c_fl, c_p]),
     "msm_l2_prefetch": (c_i, [c_p, c_p, c_i, c_p]),
     "msm_dec_set_prefetch": (c_i, [c_p, c_p, c_i]),
-    "msm_ms_seed_workspace": (c_l, [c_i]),
-    "msm_ms_select_seeds": (c_i, [c_f, c_i, c_i, c_i, c_l, c_f, c_p, c_f, c_l, c_i, c_p]),
+    "msm_ms_seed_workspace": (c_l, [c_i, c_i]),
+    "msm_ms_select_seeds": (c_i, [c_f, c_i, c_i, c_i, c_i, c_p, c_l, c_f, c_p, c_f, c_l, c_i, ctypes.c_uint64, c_p]),
     "msm_ms_hill_climb_workspace": (c_l, [c_i, c_i]),
-    "msm_ms_hill_climb": (c_i, [c_f, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
+    "msm_ms_hill_climb": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
     "msm_ms_hill_climb_split_workspace": (c_l, [c_i, c_i]),
     "msm_ms_hill_climb_split": (c_i, [c_f, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
     "msm_ms_bf16_rows": (c_l, [c_i]),
     "msm_ms_pack_bf16": (c_i, [c_f, c_i, c_i, c_p, c_p]),
     "msm_ms_select_seeds_bf16": (c_i, [c_p, c_f, c_i, c_i, c_i, c_l, c_f, c_p, c_f, c_l, c_i, c_p]),
     "msm_ms_hill_climb_bf16": (c_i, [c_p, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
-    "msm_ms_assign": (c_i, [c_f, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_i, c_p]),
-    "msm_ms_connected_components": (c_i, [c_f, c_i, c_i, c_fl, c_p, c_p, c_p]),
-    "msm_ms_relabel_largest_zero": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p]),
-    "msm_ms_seed_batched_workspace": (c_l, [c_i, c_i]),
-    "msm_ms_select_seeds_batched": (c_i, [c_f, c_i, c_i, c_i, c_i, c_p, c_f, c_p, c_f, c_l, c_i, ctypes.c_uint64, c_p]),
-    "msm_ms_hill_climb_batched_workspace": (c_l, [c_i, c_i, c_i]),
-    "msm_ms_hill_climb_batched": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
-    "msm_ms_assign_batched": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_i, c_p]),
-    "msm_ms_connected_components_batched": (c_i, [c_f, c_i, c_i, c_i, c_fl, c_p, c_p, c_p]),
-    "msm_ms_relabel_largest_zero_batched": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_p]),
+    "msm_ms_assign": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_i, c_p]),
+    "msm_ms_connected_components": (c_i, [c_f, c_i, c_i, c_i, c_fl, c_p, c_p, c_p]),
+    "msm_ms_relabel_largest_zero": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_p]),
     "msm_topk_class_scores": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]),
     "msm_topk_class_scores_gather": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_l, c_i, c_f, c_p]),
     "msm_conv1x1_in_f32": (c_i, [c_f, c_f, c_f, c_f, c_l, c_p, c_i, c_i, c_i, c_i, c_p]),

@@ -134,19 +134,12 @@ __device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, i
     }
 }
 
+// The step for M maps of one size in one launch: map = blockIdx.y, X [M][n][64], keys [M][key_stride], nearest [M][n].  A map's
+// workgroups run ms_seed_step_body on the map's own pointers, so its keys do not depend on M.
 template <bool SMALL>
 __global__ __launch_bounds__(256) void ms_seed_step_kernel(const float* __restrict__ X, int n,
-                                                           unsigned long long* __restrict__ keys, int step,
+                                                           unsigned long long* __restrict__ keys, int key_stride, int step,
                                                            float* __restrict__ nearest) {
-    ms_seed_step_body<SMALL>(X, n, keys, step, nearest);
-}
-
-// The step for M maps of one size in one launch: map = blockIdx.y, X [M][n][64], keys [M][key_stride], nearest [M][n].  A map's
-// workgroups run ms_seed_step_body on the map's own pointers, so its keys are those of the single-map launch.
-template <bool SMALL>
-__global__ __launch_bounds__(256) void ms_seed_step_batched_kernel(const float* __restrict__ X, int n,
-                                                                   unsigned long long* __restrict__ keys, int key_stride, int step,
-                                                                   float* __restrict__ nearest) {
     const int64_t m = blockIdx.y;
     ms_seed_step_body<SMALL>(X + m * n * MS_D, n, keys + m * key_stride, step, nearest + m * n);
 }
@@ -308,7 +301,7 @@ __device__ __forceinline__ float butterfly16(float (&p)[16], int j) {
 // most one step ahead of the slowest (its next sweep needs everybody's next store), so a slot is never overwritten before
 // every sweep of its previous use is over.  Called by one whole wave; returns the step's winner, `gave_up` set when the
 // bounded wait ran out (or another workgroup raised status[1]).
-// Grouped launches (ms_seed_persistent_grouped_kernel: several maps share one launch) confine the exchange to one map's
+// ms_seed_persistent_kernel (several maps may share one launch) confines the exchange to one map's
 // workgroups: a workgroup publishes in slot `slot0 + wg` and sweeps slots [slot0, slot0 + nwg) only, and `status` is the map's
 // own pair of words, so a group that gives up abandons its own map and nobody else's.  A whole launch is slot0 = 0,
 // nwg = gridDim.x, wg = blockIdx.x.
@@ -441,28 +434,21 @@ __device__ __forceinline__ void ms_seed_persistent_body(const float* __restrict_
     }
 }
 
+// ---- several small maps share one launch ---------------------------------------------------------------------------------------
+// A 224 x 224 crop (n = 50 176) needs G = cdiv(n, 512 NG) = 33 workgroups at NG = 3: alone it pays the S - 1 dependent exchanges
+// with seven eighths of the CUs empty.  So map `blockIdx.y` of the launch is held by the group of G = gridDim.x consecutive workgroups
+// [map * G, map * G + G), `maps` <= floor(CUs / G) maps per launch (one map: the group is the grid), so the launch never exceeds
+// the CU count and every workgroup is resident.  (The grid is (G, maps), not maps * G with a division: the same workgroups in the
+// same order, but one map then measured 12 us slower at 200 workgroups.)  The groups never wait for each other: a group exchanges
+// through its own slots of `gran`, gives up through its own status words (map m: status[2 m + 1]) and writes its own keys
+// (keys [M][key_stride]).  A step's winner is a maximum over (value, ~index) keys, which does not depend on how rows are split
+// into workgroups: the indices are the same for any NG and any number of maps per launch.
 template <int NG>
 __global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_kernel(const float* __restrict__ X, int n,
-                                                                     unsigned long long* __restrict__ keys, int num_seeds,
-                                                                     unsigned int* __restrict__ status /* [1] abort */,
-                                                                     unsigned long long* __restrict__ gran /* [2][2][PS_MAXWG] */) {
-    ms_seed_persistent_body<NG>(X, n, keys, num_seeds, status, gran, 0, (int)gridDim.x, (int)blockIdx.x);
-}
-
-// ---- grouped persistent seeding: several small maps share one launch -----------------------------------------------------------
-// A 224 x 224 crop (n = 50 176) needs G = cdiv(n, 512 NG) = 33 workgroups at NG = 3: alone it pays the S - 1 dependent exchanges
-// with seven eighths of the CUs empty.  Here map `blockIdx.x / G` of the launch is held by the group of G consecutive workgroups
-// [map * G, map * G + G), `maps` <= floor(CUs / G) maps per launch, so the launch still never exceeds the CU count and every
-// workgroup is resident (the argument of ms_seed_persistent_kernel).  The groups never wait for each other: a group exchanges
-// through its own slots of `gran`, gives up through its own status words (map m: status[2 m + 1]) and writes its own keys
-// (keys [M][key_stride]).  Per row the arithmetic is ms_seed_persistent_body's, and a step's winner is a maximum over (value,
-// ~index) keys, which does not depend on how rows are split into workgroups: the indices equal the single-map launch's for any NG.
-template <int NG>
-__global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_grouped_kernel(const float* __restrict__ X, int n, int G,
-                                                                             unsigned long long* __restrict__ keys, int key_stride,
-                                                                             int num_seeds, unsigned int* __restrict__ status,
-                                                                             unsigned long long* __restrict__ gran) {
-    const int m = blockIdx.x / G, wg = blockIdx.x - m * G;      // the pointers already start at the launch's first map
+                                                                     unsigned long long* __restrict__ keys, int key_stride,
+                                                                     int num_seeds, unsigned int* __restrict__ status,
+                                                                     unsigned long long* __restrict__ gran) {
+    const int m = blockIdx.y, G = gridDim.x, wg = blockIdx.x;      // the pointers already start at the launch's first map
     ms_seed_persistent_body<NG>(X + (int64_t)m * n * MS_D, n, keys + (int64_t)m * key_stride, num_seeds, status + 2 * m, gran, m * G, G, wg);
 }
 
@@ -597,47 +583,26 @@ __global__ __launch_bounds__(PS_W * 64) void ms_seed_persistent_bf16_kernel(cons
     }
 }
 
-__global__ void ms_seed_status_init_kernel(unsigned int* __restrict__ status, unsigned int give_up, unsigned long long* __restrict__ gran) {
-    if (threadIdx.x < 2) status[threadIdx.x] = threadIdx.x == 1 ? give_up : 0u;
-    for (int i = threadIdx.x; i < 4 * PS_MAXWG; i += blockDim.x) gran[i] = 0ull;     // tag 0 = no step: polled words are re-initialised every call
-}
-
-__global__ void ms_seed_init_kernel(unsigned long long* __restrict__ keys, int num_seeds, int64_t first) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < num_seeds) keys[i] = i == 0 ? (0xFFFFFFFF00000000ull | (unsigned long long)(0xFFFFFFFFu - (unsigned int)first)) : 0ull;
-}
-
-__global__ void ms_seed_finish_kernel(const float* __restrict__ X, const unsigned long long* __restrict__ keys,
-                                      int64_t* __restrict__ sel, float* __restrict__ seeds, const unsigned int* __restrict__ status,
-                                      int n) {
-    const int i = blockIdx.x;
-    unsigned int idx = 0xFFFFFFFFu - (unsigned int)(keys[i] & 0xFFFFFFFFull);
-    if ((status && status[1] != 0u) || idx >= (unsigned int)n) {      // persistent kernel gave up: report, do not fabricate
-        if (threadIdx.x == 0) sel[i] = -1;
-        idx = 0;
-    } else if (threadIdx.x == 0) sel[i] = (int64_t)idx;
-    if (threadIdx.x < MS_D) seeds[(int64_t)i * MS_D + threadIdx.x] = X[(int64_t)idx * MS_D + threadIdx.x];
-}
-
-// ---- the same three for M maps: keys [M][key_stride], status [M][2], first_index [M] (device), sel [M][S], seeds [M][S][64] ----
+// ---- keys [M][key_stride], status [M][2], sel [M][S], seeds [M][S][64]; map = blockIdx.y ----
 // gran: one [2][2][PS_MAXWG] block per persistent launch of the call (a later launch must not meet the tags of an earlier one)
-__global__ void ms_seed_status_init_batched_kernel(unsigned int* __restrict__ status, int M, unsigned long long give_up_mask,
-                                                   unsigned long long* __restrict__ gran, int64_t gran_words) {
+__global__ void ms_seed_status_init_kernel(unsigned int* __restrict__ status, int M, unsigned long long give_up_mask,
+                                           unsigned long long* __restrict__ gran, int64_t gran_words) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = t; i < 2 * (int64_t)M; i += nt) status[i] = (i & 1) ? (unsigned int)((give_up_mask >> ((i >> 1) & 63)) & 1ull) : 0u;
-    for (int64_t i = t; i < gran_words; i += nt) gran[i] = 0ull;
+    for (int64_t i = t; i < gran_words; i += nt) gran[i] = 0ull;     // tag 0 = no step: polled words are re-initialised every call
 }
 
-__global__ void ms_seed_init_batched_kernel(unsigned long long* __restrict__ keys, int key_stride, int num_seeds,
-                                            const int64_t* __restrict__ first, int n) {
+// first index of map m: first[m] (device), or the host scalar `first_host` when `first` is null (one map)
+__global__ void ms_seed_init_kernel(unsigned long long* __restrict__ keys, int key_stride, int num_seeds,
+                                    const int64_t* __restrict__ first, int64_t first_host, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
-    const int64_t f = min(max(first[m], (int64_t)0), (int64_t)n - 1);     // callers check the range; never index outside the map
+    const int64_t f = min(max(first ? first[m] : first_host, (int64_t)0), (int64_t)n - 1);     // callers check the range; never index outside the map
     if (i < num_seeds) keys[(int64_t)m * key_stride + i] = i == 0 ? (0xFFFFFFFF00000000ull | (unsigned long long)(0xFFFFFFFFu - (unsigned int)f)) : 0ull;
 }
 
-__global__ void ms_seed_finish_batched_kernel(const float* __restrict__ X, const unsigned long long* __restrict__ keys, int key_stride,
-                                              int64_t* __restrict__ sel, float* __restrict__ seeds, const unsigned int* __restrict__ status,
-                                              int n) {
+__global__ void ms_seed_finish_kernel(const float* __restrict__ X, const unsigned long long* __restrict__ keys, int key_stride,
+                                      int64_t* __restrict__ sel, float* __restrict__ seeds, const unsigned int* __restrict__ status,
+                                      int n) {
     const int i = blockIdx.x, S = gridDim.x;
     const int64_t m = blockIdx.y;
     X += m * n * MS_D;
@@ -784,17 +749,10 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
 
 #undef MS_LOAD_SLAB
 
+// M maps of one size: map = blockIdx.y, the per-map grid (gridDim.x) and slab walk do not depend on M, so neither do a map's
+// partials nor, after ms_hill_finish_kernel, its Z.  Z and part advance by z_stride / part_stride floats per map.
 template <int NSB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z,
-                                                      int S, float kappa, float* __restrict__ part) {
-    ms_hill_body<NSB>(X, n, Z, S, kappa, part);
-}
-
-// M maps of one size: map = blockIdx.y, the per-map grid (gridDim.x) and slab walk are the single-map launch's, so a map's
-// partials -- and after ms_hill_finish_batched_kernel its Z -- are bitwise those of msm_ms_hill_climb.  Z and part advance by
-// z_stride / part_stride floats per map.
-template <int NSB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_batched_kernel(const float* __restrict__ X, int n,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_kernel(const float* __restrict__ X, int n,
                                                       const float* __restrict__ Z, int64_t z_stride, int S, float kappa,
                                                       float* __restrict__ part, int64_t part_stride) {
     const int64_t m = blockIdx.y;
@@ -1368,13 +1326,9 @@ __device__ __forceinline__ void ms_hill_finish_body(const float* __restrict__ pa
     }
 }
 
-__global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __restrict__ part, int nwg, int rows_padded,
-                                                              float* __restrict__ Z) {
-    ms_hill_finish_body(part, nwg, rows_padded, Z);
-}
-
-__global__ __launch_bounds__(1024) void ms_hill_finish_batched_kernel(const float* __restrict__ part, int64_t part_stride, int nwg,
-                                                                      int rows_padded, float* __restrict__ Z, int64_t z_stride) {
+// map = blockIdx.y (the single-map split / planes / bf16 climbs: one map, strides 0)
+__global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __restrict__ part, int64_t part_stride, int nwg,
+                                                              int rows_padded, float* __restrict__ Z, int64_t z_stride) {
     const int64_t m = blockIdx.y;
     ms_hill_finish_body(part + m * part_stride, nwg, rows_padded, Z + m * z_stride);
 }
@@ -1459,14 +1413,9 @@ __device__ __forceinline__ void ms_components_body(const float* __restrict__ Z, 
     }
 }
 
-__global__ __launch_bounds__(64) void ms_components_kernel(const float* __restrict__ Z, int S, float eps, int64_t* __restrict__ labels_out,
-                                                           int32_t* __restrict__ num_out) {
-    ms_components_body(Z, S, eps, labels_out, num_out);
-}
-
 // one wave per map: Z [M][S][64], labels_out [M][S], num_out [M][2]
-__global__ __launch_bounds__(64) void ms_components_batched_kernel(const float* __restrict__ Z, int S, float eps,
-                                                                   int64_t* __restrict__ labels_out, int32_t* __restrict__ num_out) {
+__global__ __launch_bounds__(64) void ms_components_kernel(const float* __restrict__ Z, int S, float eps,
+                                                           int64_t* __restrict__ labels_out, int32_t* __restrict__ num_out) {
     const int64_t m = blockIdx.x;
     ms_components_body(Z + m * S * MS_D, S, eps, labels_out + m * S, num_out + 2 * m);
 }
@@ -1533,18 +1482,11 @@ __device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int 
         if (hist[i]) atomicAdd(&counts[i], (unsigned long long)hist[i]);
 }
 
+// map = blockIdx.y: X [M][n][64], Z [M][S][64], seed_labels [M][S], labels_out [M][n], counts [M][num_labels]
 __global__ __launch_bounds__(256) void ms_assign_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
                                                         int nchunks, const int64_t* __restrict__ seed_labels,
                                                         int64_t* __restrict__ labels_out,
                                                         unsigned long long* __restrict__ counts, int num_labels) {
-    ms_assign_body(X, n, Z, S, nchunks, seed_labels, labels_out, counts, num_labels);
-}
-
-// map = blockIdx.y: X [M][n][64], Z [M][S][64], seed_labels [M][S], labels_out [M][n], counts [M][num_labels]
-__global__ __launch_bounds__(256) void ms_assign_batched_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
-                                                                int nchunks, const int64_t* __restrict__ seed_labels,
-                                                                int64_t* __restrict__ labels_out,
-                                                                unsigned long long* __restrict__ counts, int num_labels) {
     const int64_t m = blockIdx.y;
     ms_assign_body(X + m * n * MS_D, n, Z + m * S * MS_D, S, nchunks, seed_labels + m * S, labels_out + m * n, counts + m * num_labels,
                    num_labels);
@@ -1570,14 +1512,9 @@ __device__ __forceinline__ void ms_relabel_body(int64_t* __restrict__ labels, in
     }
 }
 
+// map = blockIdx.y: labels [M][n], counts [M][num_labels], num_alive [M][2] (or null; element 0 of a map's pair is the one read)
 __global__ __launch_bounds__(256) void ms_relabel_kernel(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
                                                          int num_labels, const int32_t* __restrict__ num_alive) {
-    ms_relabel_body(labels, n, counts, num_labels, num_alive);
-}
-
-// map = blockIdx.y: labels [M][n], counts [M][num_labels], num_alive [M][2] (or null)
-__global__ __launch_bounds__(256) void ms_relabel_batched_kernel(int64_t* __restrict__ labels, int n, const int64_t* __restrict__ counts,
-                                                                 int num_labels, const int32_t* __restrict__ num_alive) {
     const int64_t m = blockIdx.y;
     ms_relabel_body(labels + m * n, n, counts + m * num_labels, num_labels, num_alive ? num_alive + 2 * m : nullptr);
 }
@@ -1595,121 +1532,169 @@ static int hill_chunk(int nsb) {
 }
 static int hill_wgs(int n) { return max(1, min(512, ((n + 15) / 16 + 3) / 4)); }
 
+// CU count of the CURRENT device (a process may drive several): cached per device ordinal
+static int device_cus() {
+    static int cu_cache[64] = {0};
+    int dev = 0, n_cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 64 && cu_cache[dev] > 0) return cu_cache[dev];
+    if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 64) cu_cache[dev] = n_cus;
+    return n_cus;
+}
+
+constexpr int MSB_KEYS = MS_SB * 16;           // key words per map
+constexpr int MSB_MAXM = 65535;                // maps per call (gridDim.y)
+constexpr int PSG_NG = 3;                      // 16-row tiles per lane group when maps share a launch: the fewest workgroups per map
+constexpr int PS_GRAN = 2 * 2 * PS_MAXWG;      // u64 words of one persistent launch's exchange block
+
+// The seeding workspace, in floats: keys [M][304] u64 | status [M][2] | gran [M][PS_GRAN] u64 (one block per persistent launch, at
+// most M: a later launch must not meet the tags of an earlier one) | nearest [M][n] (stepwise path; the bf16 persistent kernel's
+// streamed tail).  keys and gran start at even float offsets: 8-byte aligned when the workspace is.
+struct SeedWorkspace {
+    unsigned long long* keys;
+    unsigned int* status;
+    unsigned long long* gran;
+    float* nearest;
+};
+static SeedWorkspace seed_workspace(float* ws, int M) {
+    return {reinterpret_cast<unsigned long long*>(ws), reinterpret_cast<unsigned int*>(ws + (int64_t)M * 2 * MSB_KEYS),
+            reinterpret_cast<unsigned long long*>(ws + (int64_t)M * (2 * MSB_KEYS + 2)), ws + (int64_t)M * (2 * MSB_KEYS + 2 + 2 * PS_GRAN)};
+}
+
+// The hill climb's walk over chunks of seed blocks, for M maps whose Z / partial sums lie z_stride / part_stride floats apart.
+// Per iteration: every chunk's partial sums ([G][nb * 16][64] per map, issued by `launch(Zc, Sc, nb, ws)`; all chunks of one
+// iteration read the same Z), then the finish launches.
+template <class Launch>
+static int hill_iterations(float* Z, int M, int64_t z_stride, int S, int iters, float* parts, int64_t part_stride, int G, hipStream_t st,
+                           Launch launch) {
+    const int nsb = cdiv(S, 16);
+    const int CH = hill_chunk(nsb);
+    for (int it = 0; it < iters; ++it) {
+        float* ws = parts;
+        for (int b0 = 0; b0 < nsb; b0 += CH) {
+            const int nb = min(CH, nsb - b0);
+            const int rc = launch(Z + (int64_t)b0 * 16 * MS_D, min(S - b0 * 16, nb * 16), nb, ws);
+            if (rc != MSM_OK) return rc;
+            ws += (int64_t)G * nb * 16 * MS_D;
+        }
+        ws = parts;
+        for (int b0 = 0; b0 < nsb; b0 += CH) {
+            const int nb = min(CH, nsb - b0);
+            const int Sc = min(S - b0 * 16, nb * 16);
+            hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(Sc, M), dim3(1024), 0, st, ws, part_stride, G, nb * 16, Z + (int64_t)b0 * 16 * MS_D,
+                               z_stride);
+            ws += (int64_t)G * nb * 16 * MS_D;
+        }
+    }
+    return MSM_OK;
+}
+
 }  // namespace msm
 
 using namespace msm;
 
-// keys [S] u64 | 8 words (2 used: barrier arrivals, abort flag) | nearest [n] (stepwise path)
-extern "C" int64_t msm_ms_seed_workspace(int n) { return (int64_t)n + 2 * (MS_SB * 16) + 16; }
+extern "C" int64_t msm_ms_seed_workspace(int M, int n) { return (int64_t)M * (2 * MSB_KEYS + 2 + 2 * PS_GRAN + (int64_t)n); }
 
-extern "C" int msm_ms_select_seeds(const float* X, int n, int d, int num_seeds, int64_t first_index, float* seeds_out,
-                                   int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags, void* stream) {
+extern "C" int msm_ms_select_seeds(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices, int64_t first_index,
+                                   float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags,
+                                   uint64_t test_give_up_mask, void* stream) {
     MSM_REQUIRE(X && seeds_out && indices_out && workspace, "msm_ms_select_seeds: null pointer");
     MSM_REQUIRE(d == MS_D, "msm_ms_select_seeds: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(n > 0 && num_seeds > 0 && first_index >= 0 && first_index < n, "msm_ms_select_seeds: bad sizes");
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && num_seeds > 0, "msm_ms_select_seeds: bad sizes (1 <= M <= %d)", MSB_MAXM);
+    MSM_REQUIRE(first_indices || (M == 1 && first_index >= 0 && first_index < n),
+                "msm_ms_select_seeds: first_indices [M] on the device or, for one map, first_index in [0, n)");
+    MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds: at most %d seeds", MS_SB * 16);
     MSM_REQUIRE((((uintptr_t)X) & 15) == 0 && (((uintptr_t)workspace) & 7) == 0, "msm_ms_select_seeds: misaligned pointer");
-    if (workspace_elems < msm_ms_seed_workspace(n)) {
+    if (workspace_elems < msm_ms_seed_workspace(M, n)) {
         set_error("msm_ms_select_seeds: workspace too small");
         return MSM_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds: at most %d seeds", MS_SB * 16);
-    const int nblk = seed_blocks(n);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);       // [num_seeds]
-    float* nearest = workspace + 2 * (MS_SB * 16) + 8;
-    hipLaunchKernelGGL(ms_seed_init_kernel, dim3(cdiv(num_seeds, 64)), dim3(64), 0, st, keys, num_seeds, first_index);
-    // persistent single-launch path when the map fits the register files of the CUs (see ms_seed_persistent_kernel)
-    // CU count of the CURRENT device (a process may drive several): cached per device ordinal
-    static int cu_cache[64] = {0};
-    int dev = 0, n_cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        if (dev >= 0 && dev < 64 && cu_cache[dev] > 0) n_cus = cu_cache[dev];
-        else if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
-            if (dev >= 0 && dev < 64) cu_cache[dev] = n_cus;
-        } else n_cus = 0;
-    }
-    const int ng = cdiv(n, 256 * PS_W * 64);                       // rows per workgroup = 512 * ng
-    const int pgrid = ng >= 1 && ng <= 3 ? cdiv(n, PS_W * 64 * ng) : 0;
-    unsigned int* status = reinterpret_cast<unsigned int*>(workspace + 2 * (MS_SB * 16) + 4);   // 2 words between keys and nearest
-    if (pgrid > 0 && pgrid <= n_cus && pgrid <= PS_MAXWG && n >= 4096 && num_seeds > 2 && !(flags & MSM_MS_SEED_STEPWISE) &&
-        opt(MSM_OPT_MS_NO_PERSISTENT) != 1) {
-        // the exchange slots live where the stepwise path keeps nearest[] (unused here): 2 parities x 2 granule rows x 256 slots x 8 B = 8 KiB
-        unsigned long long* gran = reinterpret_cast<unsigned long long*>(nearest);
-        hipLaunchKernelGGL(ms_seed_status_init_kernel, dim3(1), dim3(256), 0, st, status, (flags & MSM_MS_SEED_TEST_GIVE_UP) ? 1u : 0u, gran);
-        switch (ng) {
-            case 1: hipLaunchKernelGGL(ms_seed_persistent_kernel<1>, dim3(pgrid), dim3(PS_W * 64), 0, st, X, n, keys, num_seeds, status, gran); break;
-            case 2: hipLaunchKernelGGL(ms_seed_persistent_kernel<2>, dim3(pgrid), dim3(PS_W * 64), 0, st, X, n, keys, num_seeds, status, gran); break;
-            default: hipLaunchKernelGGL(ms_seed_persistent_kernel<3>, dim3(pgrid), dim3(PS_W * 64), 0, st, X, n, keys, num_seeds, status, gran); break;
+    const SeedWorkspace w = seed_workspace(workspace, M);
+    hipLaunchKernelGGL(ms_seed_init_kernel, dim3(cdiv(num_seeds, 64), M), dim3(64), 0, st, w.keys, MSB_KEYS, num_seeds, first_indices, first_index,
+                       n);
+    // Persistent launches while a map's group of G workgroups fits the chip (see ms_seed_persistent_kernel).  One map spreads over
+    // the workgroups that hold it with the fewest tiles (ng = 1 .. 3: up to 393 216 rows); several maps take the fewest workgroups
+    // each (224 x 224: 33) and share launches.  A launch never exceeds the CU count: the exchange spins, so every workgroup of it
+    // must be resident.
+    const int ng = M == 1 ? cdiv(n, 256 * PS_W * 64) : PSG_NG;     // rows per workgroup = 512 * ng
+    const int G = ng <= 3 ? cdiv(n, PS_W * 64 * ng) : 0;
+    const int wg_cap = min(device_cus(), PS_MAXWG);
+    if (G > 0 && G <= wg_cap && n >= 4096 && num_seeds > 2 && !(flags & MSM_MS_SEED_STEPWISE) && opt(MSM_OPT_MS_NO_PERSISTENT) != 1) {
+        const int per = wg_cap / G;                                 // maps per launch
+        const int launches = cdiv(M, per);
+        hipLaunchKernelGGL(ms_seed_status_init_kernel, dim3(min(64, cdiv(launches * PS_GRAN, 256))), dim3(256), 0, st, w.status, M,
+                           (flags & MSM_MS_SEED_TEST_GIVE_UP) ? (unsigned long long)test_give_up_mask : 0ull, w.gran, (int64_t)launches * PS_GRAN);
+        for (int l = 0; l < launches; ++l) {
+            const int m0 = l * per, maps = min(per, M - m0);
+            const dim3 grid(G, maps), block(PS_W * 64);
+            const float* Xl = X + (int64_t)m0 * n * MS_D;
+            unsigned long long* kl = w.keys + (int64_t)m0 * MSB_KEYS;
+            unsigned int* sl = w.status + 2 * m0;
+            unsigned long long* gl = w.gran + (int64_t)l * PS_GRAN;
+            switch (ng) {
+                case 1: hipLaunchKernelGGL(ms_seed_persistent_kernel<1>, grid, block, 0, st, Xl, n, kl, MSB_KEYS, num_seeds, sl, gl); break;
+                case 2: hipLaunchKernelGGL(ms_seed_persistent_kernel<2>, grid, block, 0, st, Xl, n, kl, MSB_KEYS, num_seeds, sl, gl); break;
+                default: hipLaunchKernelGGL(ms_seed_persistent_kernel<3>, grid, block, 0, st, Xl, n, kl, MSB_KEYS, num_seeds, sl, gl); break;
+            }
         }
-        hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds), dim3(64), 0, st, X, keys, indices_out, seeds_out, status, n);
+        hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, w.keys, MSB_KEYS, indices_out, seeds_out, w.status, n);
         MSM_CHECK_LAUNCH("msm_ms_select_seeds(persistent)");
         return MSM_OK;
     }
+    const int nblk = seed_blocks(n);
     for (int i = 1; i < num_seeds; ++i)
-        if (n >= 16) hipLaunchKernelGGL(ms_seed_step_kernel<false>, dim3(nblk), dim3(256), 0, st, X, n, keys, i, nearest);
-        else hipLaunchKernelGGL(ms_seed_step_kernel<true>, dim3(nblk), dim3(256), 0, st, X, n, keys, i, nearest);
-    hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds), dim3(64), 0, st, X, keys, indices_out, seeds_out,
+        if (n >= 16) hipLaunchKernelGGL(ms_seed_step_kernel<false>, dim3(nblk, M), dim3(256), 0, st, X, n, w.keys, MSB_KEYS, i, w.nearest);
+        else hipLaunchKernelGGL(ms_seed_step_kernel<true>, dim3(nblk, M), dim3(256), 0, st, X, n, w.keys, MSB_KEYS, i, w.nearest);
+    hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, w.keys, MSB_KEYS, indices_out, seeds_out,
                        (const unsigned int*)nullptr, n);
     MSM_CHECK_LAUNCH("msm_ms_select_seeds");
     return MSM_OK;
 }
 
+// partial sums of ONE map's workgroups
 extern "C" int64_t msm_ms_hill_climb_workspace(int n, int S) {
     const int nsb = cdiv(S, 16);
     return (int64_t)hill_wgs(n) * nsb * 16 * MS_D;
 }
 
 template <int NSB>
-static int hill_chunk_launch(const float* X, int n, const float* Zc, int Sc, float kappa, float* ws, int G, hipStream_t st) {
+static int hill_chunk_launch(const float* X, int M, int n, const float* Zc, int64_t z_stride, int Sc, float kappa, float* ws,
+                             int64_t part_stride, int G, hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)NSB * 16 * SZ + 4 * 16 * SZ);
     MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_hill_kernel<NSB>, lds));
-    hipLaunchKernelGGL((ms_hill_kernel<NSB>), dim3(G), dim3(256), lds, st, X, n, Zc, Sc, kappa, ws);
+    hipLaunchKernelGGL((ms_hill_kernel<NSB>), dim3(G, M), dim3(256), lds, st, X, n, Zc, z_stride, Sc, kappa, ws, part_stride);
     return MSM_OK;
 }
 
-extern "C" int msm_ms_hill_climb(const float* X, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
+extern "C" int msm_ms_hill_climb(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
                                  int64_t workspace_elems, void* stream) {
     MSM_REQUIRE(X && Z && workspace, "msm_ms_hill_climb: null pointer");
     MSM_REQUIRE(d == MS_D, "msm_ms_hill_climb: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0, "msm_ms_hill_climb: bad sizes (S <= %d)", MS_SB * 16);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0,
+                "msm_ms_hill_climb: bad sizes (S <= %d, M <= %d)", MS_SB * 16, MSB_MAXM);
     MSM_REQUIRE((((uintptr_t)X) & 15) == 0, "msm_ms_hill_climb: X must be 16-byte aligned");
-    if (workspace_elems < msm_ms_hill_climb_workspace(n, S)) {
+    const int64_t z_stride = (int64_t)S * MS_D, part_stride = msm_ms_hill_climb_workspace(n, S);
+    if (workspace_elems < M * part_stride) {
         set_error("msm_ms_hill_climb: workspace too small");
         return MSM_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
     const int G = hill_wgs(n);
-    const int nsb = cdiv(S, 16);
-    const int CH = hill_chunk(nsb);
-    for (int it = 0; it < iters; ++it) {
-        // all chunks of one iteration read the same Z; the finish kernels run after every chunk
-        float* ws = workspace;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const float* Zc = Z + (int64_t)b0 * 16 * MS_D;
-            const int Sc = min(S - b0 * 16, nb * 16);
-            int rc = MSM_OK;
-            switch (nb) {
-                case 1: rc = hill_chunk_launch<1>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 2: rc = hill_chunk_launch<2>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 3: rc = hill_chunk_launch<3>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 4: rc = hill_chunk_launch<4>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 5: rc = hill_chunk_launch<5>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 6: rc = hill_chunk_launch<6>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                case 7: rc = hill_chunk_launch<7>(X, n, Zc, Sc, kappa, ws, G, st); break;
-                default: rc = hill_chunk_launch<8>(X, n, Zc, Sc, kappa, ws, G, st); break;
-            }
-            if (rc != MSM_OK) return rc;
-            ws += (int64_t)G * nb * 16 * MS_D;
+    const int rc = hill_iterations(Z, M, z_stride, S, iters, workspace, part_stride, G, st, [&](const float* Zc, int Sc, int nb, float* ws) {
+        switch (nb) {
+            case 1: return hill_chunk_launch<1>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 2: return hill_chunk_launch<2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 3: return hill_chunk_launch<3>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 4: return hill_chunk_launch<4>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 5: return hill_chunk_launch<5>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 6: return hill_chunk_launch<6>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 7: return hill_chunk_launch<7>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            default: return hill_chunk_launch<8>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
         }
-        ws = workspace;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const int Sc = min(S - b0 * 16, nb * 16);
-            hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(Sc), dim3(1024), 0, st, ws, G, nb * 16, Z + (int64_t)b0 * 16 * MS_D);
-            ws += (int64_t)G * nb * 16 * MS_D;
-        }
-    }
+    });
+    if (rc != MSM_OK) return rc;
     MSM_CHECK_LAUNCH("msm_ms_hill_climb");
     return MSM_OK;
 }
@@ -1753,8 +1738,6 @@ extern "C" int msm_ms_hill_climb_split(const float* X, int n, int d, float* Z, i
     // the partial-sum region is sized for those)
     const int nslabs = cdiv(n, HS_ROWS);
     const int G = max(1, min(256, cdiv(nslabs, 4)));
-    const int nsb = cdiv(S, 16);
-    const int CH = hill_chunk(nsb);
     const bool planes = opt(MSM_OPT_MS_SPLIT_KERNEL) != 1;         // 1: X split inside the iteration kernel (fallback, no pre-pass)
     const int64_t n_pad = (int64_t)nslabs * HS_ROWS;
     uint16_t* Xp = reinterpret_cast<uint16_t*>(workspace);
@@ -1762,39 +1745,23 @@ extern "C" int msm_ms_hill_climb_split(const float* X, int n, int d, float* Z, i
     if (planes && iters > 0)
         hipLaunchKernelGGL(ms_split_planes_kernel, dim3((unsigned)min((int64_t)2048, (n_pad * (MS_D / 4) + 255) / 256)), dim3(256), 0, st, X, n,
                            (int)n_pad, Xp);
-    for (int it = 0; it < iters; ++it) {
-        float* ws = parts;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const float* Zc = Z + (int64_t)b0 * 16 * MS_D;
-            const int Sc = min(S - b0 * 16, nb * 16);
-            int rc = MSM_OK;
-            if (planes) {
-                switch ((nb + 1) / 2) {
-                    case 1: rc = hill_planes_launch<1>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    case 2: rc = hill_planes_launch<2>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    case 3: rc = hill_planes_launch<3>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    default: rc = hill_planes_launch<4>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                }
-            } else {
-                switch ((nb + 1) / 2) {
-                    case 1: rc = hill_split_launch<1>(X, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    case 2: rc = hill_split_launch<2>(X, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    case 3: rc = hill_split_launch<3>(X, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                    default: rc = hill_split_launch<4>(X, n, Zc, Sc, nb, kappa, ws, G, st); break;
-                }
+    const int rc = hill_iterations(Z, 1, 0, S, iters, parts, 0, G, st, [&](const float* Zc, int Sc, int nb, float* ws) {
+        if (planes) {
+            switch ((nb + 1) / 2) {
+                case 1: return hill_planes_launch<1>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st);
+                case 2: return hill_planes_launch<2>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st);
+                case 3: return hill_planes_launch<3>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st);
+                default: return hill_planes_launch<4>(Xp, n_pad * MS_D, n, Zc, Sc, nb, kappa, ws, G, st);
             }
-            if (rc != MSM_OK) return rc;
-            ws += (int64_t)G * nb * 16 * MS_D;
         }
-        ws = parts;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const int Sc = min(S - b0 * 16, nb * 16);
-            hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(Sc), dim3(1024), 0, st, ws, G, nb * 16, Z + (int64_t)b0 * 16 * MS_D);
-            ws += (int64_t)G * nb * 16 * MS_D;
+        switch ((nb + 1) / 2) {
+            case 1: return hill_split_launch<1>(X, n, Zc, Sc, nb, kappa, ws, G, st);
+            case 2: return hill_split_launch<2>(X, n, Zc, Sc, nb, kappa, ws, G, st);
+            case 3: return hill_split_launch<3>(X, n, Zc, Sc, nb, kappa, ws, G, st);
+            default: return hill_split_launch<4>(X, n, Zc, Sc, nb, kappa, ws, G, st);
         }
-    }
+    });
+    if (rc != MSM_OK) return rc;
     MSM_CHECK_LAUNCH("msm_ms_hill_climb_split");
     return MSM_OK;
 }
@@ -1820,47 +1787,39 @@ extern "C" int msm_ms_select_seeds_bf16(const void* Xb, const float* X, int n, i
     MSM_REQUIRE(n >= 16 && num_seeds > 0 && first_index >= 0 && first_index < n, "msm_ms_select_seeds_bf16: bad sizes (n >= 16)");
     MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds_bf16: at most %d seeds", MS_SB * 16);
     MSM_REQUIRE((((uintptr_t)Xb) & 15) == 0 && (((uintptr_t)workspace) & 7) == 0, "msm_ms_select_seeds_bf16: misaligned pointer");
-    if (workspace_elems < msm_ms_seed_workspace(n)) {
+    if (workspace_elems < msm_ms_seed_workspace(1, n)) {
         set_error("msm_ms_select_seeds_bf16: workspace too small");
         return MSM_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);
-    float* nearest = workspace + 2 * (MS_SB * 16) + 8;
-    hipLaunchKernelGGL(ms_seed_init_kernel, dim3(cdiv(num_seeds, 64)), dim3(64), 0, st, keys, num_seeds, first_index);
+    const SeedWorkspace w = seed_workspace(workspace, 1);
+    hipLaunchKernelGGL(ms_seed_init_kernel, dim3(cdiv(num_seeds, 64), 1), dim3(64), 0, st, w.keys, MSB_KEYS, num_seeds, (const int64_t*)nullptr,
+                       first_index, n);
     // one persistent launch with the rows held in VGPRs / LDS / streamed (ms_seed_persistent_bf16_kernel): one workgroup per CU
-    // CU count of the CURRENT device (a process may drive several): cached per device ordinal
-    static int cu_cache[64] = {0};
-    int dev = 0, n_cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        if (dev >= 0 && dev < 64 && cu_cache[dev] > 0) n_cus = cu_cache[dev];
-        else if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
-            if (dev >= 0 && dev < 64) cu_cache[dev] = n_cus;
-        } else n_cus = 0;
-    }
+    const int n_cus = device_cus();
     constexpr int NG = 5, NL = 2;
     const int pgrid = min(n_cus, PS_MAXWG);
     const int tail0 = pgrid * PB_GROUPS * (NG + NL) * 16;
     if (pgrid >= 64 && n >= 65536 && (n <= tail0 || n - tail0 >= 16) && num_seeds > 2 && !(flags & MSM_MS_SEED_STEPWISE) &&
         opt(MSM_OPT_MS_NO_PERSISTENT) != 1) {
-        unsigned int* status = reinterpret_cast<unsigned int*>(workspace + 2 * (MS_SB * 16) + 4);
-        unsigned long long* gran = reinterpret_cast<unsigned long long*>(nearest);          // 8 KiB of exchange slots, then the tail's nearest[]
-        float* nearest_tail = nearest + 4 * PS_MAXWG * 2;
         const int tail_rows_per_wg = n > tail0 ? cdiv(cdiv(n - tail0, pgrid), 16) * 16 : 0;
         const size_t lds = (size_t)PB_GROUPS * (NL * 16 * 128 + 128);
         MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_seed_persistent_bf16_kernel<NG, NL>, lds));
-        hipLaunchKernelGGL(ms_seed_status_init_kernel, dim3(1), dim3(256), 0, st, status, (flags & MSM_MS_SEED_TEST_GIVE_UP) ? 1u : 0u, gran);
-        hipLaunchKernelGGL((ms_seed_persistent_bf16_kernel<NG, NL>), dim3(pgrid), dim3(PS_W * 64), lds, st, (const uint16_t*)Xb, n, keys, num_seeds,
-                           status, gran, nearest_tail, tail0, tail_rows_per_wg);
-        hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds), dim3(64), 0, st, X, keys, indices_out, seeds_out, status, n);
+        hipLaunchKernelGGL(ms_seed_status_init_kernel, dim3(cdiv(PS_GRAN, 256)), dim3(256), 0, st, w.status, 1,
+                           (flags & MSM_MS_SEED_TEST_GIVE_UP) ? 1ull : 0ull, w.gran, (int64_t)PS_GRAN);
+        // the streamed tail's nearest[] is the stepwise path's region (unused here)
+        hipLaunchKernelGGL((ms_seed_persistent_bf16_kernel<NG, NL>), dim3(pgrid), dim3(PS_W * 64), lds, st, (const uint16_t*)Xb, n, w.keys, num_seeds,
+                           w.status, w.gran, w.nearest, tail0, tail_rows_per_wg);
+        hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds, 1), dim3(64), 0, st, X, w.keys, MSB_KEYS, indices_out, seeds_out, w.status, n);
         MSM_CHECK_LAUNCH("msm_ms_select_seeds_bf16(persistent)");
         return MSM_OK;
     }
     const int nblk = seed_blocks(n);
     for (int i = 1; i < num_seeds; ++i)
-        hipLaunchKernelGGL(ms_seed_step_bf16_kernel, dim3(nblk), dim3(256), 0, st, (const uint16_t*)Xb, n, keys, i, nearest);
+        hipLaunchKernelGGL(ms_seed_step_bf16_kernel, dim3(nblk), dim3(256), 0, st, (const uint16_t*)Xb, n, w.keys, i, w.nearest);
     // the seeds handed on are rows of the caller's fp32 X (the reference returns X[selected], MS:186-189)
-    hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds), dim3(64), 0, st, X, keys, indices_out, seeds_out, (const unsigned int*)nullptr, n);
+    hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds, 1), dim3(64), 0, st, X, w.keys, MSB_KEYS, indices_out, seeds_out,
+                       (const unsigned int*)nullptr, n);
     MSM_CHECK_LAUNCH("msm_ms_select_seeds_bf16");
     return MSM_OK;
 }
@@ -1902,215 +1861,47 @@ extern "C" int msm_ms_hill_climb_bf16(const void* Xb, int n, int d, float* Z, in
             default: rc = hill_bf16_launch<10>((const uint16_t*)Xb, n, Z, S, nsb, kappa, workspace, G, st); break;
         }
         if (rc != MSM_OK) return rc;
-        hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(S), dim3(1024), 0, st, workspace, G, nsb * 16, Z);
+        hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(S, 1), dim3(1024), 0, st, workspace, (int64_t)0, G, nsb * 16, Z, (int64_t)0);
     }
     MSM_CHECK_LAUNCH("msm_ms_hill_climb_bf16");
     return MSM_OK;
 }
 
-extern "C" int msm_ms_assign(const float* X, int n, int d, const float* Z, int S, const int64_t* seed_labels,
+extern "C" int msm_ms_assign(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
                              int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
     MSM_REQUIRE(X && Z && seed_labels && labels_out && counts, "msm_ms_assign: null pointer");
     MSM_REQUIRE(d == MS_D, "msm_ms_assign: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(n > 0 && S > 0 && S <= MS_SB * 16 && num_labels > 0 && num_labels <= 4096, "msm_ms_assign: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    MSM_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)num_labels, st));
-    const int nchunks = cdiv(cdiv(S, 16), MS_CH);
-    const int G = hill_wgs(n);
-    const size_t lds = sizeof(float) * ((size_t)nchunks * MS_CH * 16 * SZ + 4 * 16 * SZ) + sizeof(unsigned int) * (size_t)num_labels;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_kernel, lds));
-    hipLaunchKernelGGL(ms_assign_kernel, dim3(G), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
-                       reinterpret_cast<unsigned long long*>(counts), num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_assign");
-    return MSM_OK;
-}
-
-extern "C" int msm_ms_connected_components(const float* Z, int S, int d, float epsilon, int64_t* seed_labels, int32_t* num_labels,
-                                           void* stream) {
-    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(S > 0 && S <= CC_MAXS, "msm_ms_connected_components: S=%d must be in 1..%d", S, CC_MAXS);
-    const size_t lds = sizeof(float) * (size_t)S * (MS_D + 1) + sizeof(int) * 2 * (size_t)S;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_kernel, lds));
-    hipLaunchKernelGGL(ms_components_kernel, dim3(1), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_connected_components");
-    return MSM_OK;
-}
-
-extern "C" int msm_ms_relabel_largest_zero(int64_t* labels, int n, const int64_t* counts, int num_labels, const int32_t* num_alive,
-                                           void* stream) {
-    MSM_REQUIRE(labels && counts && n > 0 && num_labels > 0, "msm_ms_relabel_largest_zero: bad arguments");
-    hipLaunchKernelGGL(ms_relabel_kernel, dim3(min(2048, cdiv(n, 256))), dim3(256), 0, (hipStream_t)stream, labels, n,
-                       counts, num_labels, num_alive);
-    MSM_CHECK_LAUNCH("msm_ms_relabel_largest_zero");
-    return MSM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// M maps of one size per call (the second stage of the two-stage clustering: one 224 x 224 map per object).  Exact fp32 plan only.
-// ------------------------------------------------------------------------------------------------
-static int device_cus() {
-    static int cu_cache[64] = {0};
-    int dev = 0, n_cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (dev >= 0 && dev < 64 && cu_cache[dev] > 0) return cu_cache[dev];
-    if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (dev >= 0 && dev < 64) cu_cache[dev] = n_cus;
-    return n_cus;
-}
-
-constexpr int MSB_KEYS = MS_SB * 16;           // key words per map
-constexpr int MSB_MAXM = 65535;                // maps per call (gridDim.y)
-constexpr int PSG_NG = 3;                      // 16-row tiles per lane group of the grouped launch: the fewest workgroups per map
-
-// keys [M][304] u64 | status [M][2] | gran [M][2][2][PS_MAXWG] u64 (one block per persistent launch, at most M) | nearest [M][n]
-extern "C" int64_t msm_ms_seed_batched_workspace(int M, int n) {
-    return (int64_t)M * (2 * MSB_KEYS + 2 + 2 * 4 * PS_MAXWG + (int64_t)n);
-}
-
-extern "C" int msm_ms_select_seeds_batched(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices,
-                                           float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, int flags,
-                                           uint64_t test_give_up_mask, void* stream) {
-    MSM_REQUIRE(X && first_indices && seeds_out && indices_out && workspace, "msm_ms_select_seeds_batched: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_select_seeds_batched: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && num_seeds > 0, "msm_ms_select_seeds_batched: bad sizes (1 <= M <= %d)", MSB_MAXM);
-    MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds_batched: at most %d seeds", MS_SB * 16);
-    MSM_REQUIRE((((uintptr_t)X) & 15) == 0 && (((uintptr_t)workspace) & 7) == 0, "msm_ms_select_seeds_batched: misaligned pointer");
-    if (workspace_elems < msm_ms_seed_batched_workspace(M, n)) {
-        set_error("msm_ms_select_seeds_batched: workspace too small");
-        return MSM_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);                          // [M][MSB_KEYS]
-    unsigned int* status = reinterpret_cast<unsigned int*>(workspace + (int64_t)M * 2 * MSB_KEYS);        // [M][2]
-    unsigned long long* gran = reinterpret_cast<unsigned long long*>(workspace + (int64_t)M * (2 * MSB_KEYS + 2));
-    float* nearest = workspace + (int64_t)M * (2 * MSB_KEYS + 2 + 2 * 4 * PS_MAXWG);
-    hipLaunchKernelGGL(ms_seed_init_batched_kernel, dim3(cdiv(num_seeds, 64), M), dim3(64), 0, st, keys, MSB_KEYS, num_seeds, first_indices, n);
-    // grouped persistent launches while a map's group fits the chip (see ms_seed_persistent_grouped_kernel)
-    const int n_cus = device_cus();
-    const int G = cdiv(n, PS_W * 64 * PSG_NG);
-    const int wg_cap = min(n_cus, PS_MAXWG);
-    if (G <= wg_cap && n >= 4096 && num_seeds > 2 && !(flags & MSM_MS_SEED_STEPWISE) && opt(MSM_OPT_MS_NO_PERSISTENT) != 1) {
-        const int per = wg_cap / G;                                 // maps per launch
-        const int launches = cdiv(M, per);
-        hipLaunchKernelGGL(ms_seed_status_init_batched_kernel, dim3(min(64, cdiv(launches * 4 * PS_MAXWG, 256))), dim3(256), 0, st, status, M,
-                           (flags & MSM_MS_SEED_TEST_GIVE_UP) ? (unsigned long long)test_give_up_mask : 0ull, gran,
-                           (int64_t)launches * 4 * PS_MAXWG);
-        for (int l = 0; l < launches; ++l) {
-            const int m0 = l * per, maps = min(per, M - m0);
-            hipLaunchKernelGGL(ms_seed_persistent_grouped_kernel<PSG_NG>, dim3(maps * G), dim3(PS_W * 64), 0, st, X + (int64_t)m0 * n * MS_D, n, G,
-                               keys + (int64_t)m0 * MSB_KEYS, MSB_KEYS, num_seeds, status + 2 * m0, gran + (int64_t)l * 4 * PS_MAXWG);
-        }
-        hipLaunchKernelGGL(ms_seed_finish_batched_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, keys, MSB_KEYS, indices_out, seeds_out, status, n);
-        MSM_CHECK_LAUNCH("msm_ms_select_seeds_batched(grouped)");
-        return MSM_OK;
-    }
-    const int nblk = seed_blocks(n);
-    for (int i = 1; i < num_seeds; ++i)
-        if (n >= 16) hipLaunchKernelGGL(ms_seed_step_batched_kernel<false>, dim3(nblk, M), dim3(256), 0, st, X, n, keys, MSB_KEYS, i, nearest);
-        else hipLaunchKernelGGL(ms_seed_step_batched_kernel<true>, dim3(nblk, M), dim3(256), 0, st, X, n, keys, MSB_KEYS, i, nearest);
-    hipLaunchKernelGGL(ms_seed_finish_batched_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, keys, MSB_KEYS, indices_out, seeds_out,
-                       (const unsigned int*)nullptr, n);
-    MSM_CHECK_LAUNCH("msm_ms_select_seeds_batched");
-    return MSM_OK;
-}
-
-extern "C" int64_t msm_ms_hill_climb_batched_workspace(int M, int n, int S) { return (int64_t)M * msm_ms_hill_climb_workspace(n, S); }
-
-template <int NSB>
-static int hill_chunk_launch_batched(const float* X, int M, int n, const float* Zc, int64_t z_stride, int Sc, float kappa, float* ws,
-                                     int64_t part_stride, int G, hipStream_t st) {
-    const size_t lds = sizeof(float) * ((size_t)NSB * 16 * SZ + 4 * 16 * SZ);
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_hill_batched_kernel<NSB>, lds));
-    hipLaunchKernelGGL((ms_hill_batched_kernel<NSB>), dim3(G, M), dim3(256), lds, st, X, n, Zc, z_stride, Sc, kappa, ws, part_stride);
-    return MSM_OK;
-}
-
-extern "C" int msm_ms_hill_climb_batched(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
-                                         int64_t workspace_elems, void* stream) {
-    MSM_REQUIRE(X && Z && workspace, "msm_ms_hill_climb_batched: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_hill_climb_batched: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0,
-                "msm_ms_hill_climb_batched: bad sizes (S <= %d, M <= %d)", MS_SB * 16, MSB_MAXM);
-    MSM_REQUIRE((((uintptr_t)X) & 15) == 0, "msm_ms_hill_climb_batched: X must be 16-byte aligned");
-    if (workspace_elems < msm_ms_hill_climb_batched_workspace(M, n, S)) {
-        set_error("msm_ms_hill_climb_batched: workspace too small");
-        return MSM_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = hill_wgs(n);
-    const int nsb = cdiv(S, 16);
-    const int CH = hill_chunk(nsb);
-    const int64_t z_stride = (int64_t)S * MS_D, part_stride = msm_ms_hill_climb_workspace(n, S);
-    for (int it = 0; it < iters; ++it) {
-        // as msm_ms_hill_climb: all chunks of one iteration read the same Z, the finish kernels run after every chunk
-        float* ws = workspace;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const float* Zc = Z + (int64_t)b0 * 16 * MS_D;
-            const int Sc = min(S - b0 * 16, nb * 16);
-            int rc = MSM_OK;
-            switch (nb) {
-                case 1: rc = hill_chunk_launch_batched<1>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 2: rc = hill_chunk_launch_batched<2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 3: rc = hill_chunk_launch_batched<3>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 4: rc = hill_chunk_launch_batched<4>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 5: rc = hill_chunk_launch_batched<5>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 6: rc = hill_chunk_launch_batched<6>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                case 7: rc = hill_chunk_launch_batched<7>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-                default: rc = hill_chunk_launch_batched<8>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st); break;
-            }
-            if (rc != MSM_OK) return rc;
-            ws += (int64_t)G * nb * 16 * MS_D;
-        }
-        ws = workspace;
-        for (int b0 = 0; b0 < nsb; b0 += CH) {
-            const int nb = min(CH, nsb - b0);
-            const int Sc = min(S - b0 * 16, nb * 16);
-            hipLaunchKernelGGL(ms_hill_finish_batched_kernel, dim3(Sc, M), dim3(1024), 0, st, ws, part_stride, G, nb * 16,
-                               Z + (int64_t)b0 * 16 * MS_D, z_stride);
-            ws += (int64_t)G * nb * 16 * MS_D;
-        }
-    }
-    MSM_CHECK_LAUNCH("msm_ms_hill_climb_batched");
-    return MSM_OK;
-}
-
-extern "C" int msm_ms_assign_batched(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
-                                     int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
-    MSM_REQUIRE(X && Z && seed_labels && labels_out && counts, "msm_ms_assign_batched: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_assign_batched: d=%d, only d=64 is supported", d);
     MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && num_labels > 0 && num_labels <= 4096,
-                "msm_ms_assign_batched: bad sizes");
+                "msm_ms_assign: bad sizes");
     hipStream_t st = (hipStream_t)stream;
     MSM_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)M * (size_t)num_labels, st));
     const int nchunks = cdiv(cdiv(S, 16), MS_CH);
     const int G = hill_wgs(n);
     const size_t lds = sizeof(float) * ((size_t)nchunks * MS_CH * 16 * SZ + 4 * 16 * SZ) + sizeof(unsigned int) * (size_t)num_labels;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_batched_kernel, lds));
-    hipLaunchKernelGGL(ms_assign_batched_kernel, dim3(G, M), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_kernel, lds));
+    hipLaunchKernelGGL(ms_assign_kernel, dim3(G, M), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
                        reinterpret_cast<unsigned long long*>(counts), num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_assign_batched");
+    MSM_CHECK_LAUNCH("msm_ms_assign");
     return MSM_OK;
 }
 
-extern "C" int msm_ms_connected_components_batched(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
-                                                   int32_t* num_labels, void* stream) {
-    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components_batched: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components_batched: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(M > 0 && S > 0 && S <= CC_MAXS, "msm_ms_connected_components_batched: S=%d must be in 1..%d", S, CC_MAXS);
+extern "C" int msm_ms_connected_components(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
+                                           int32_t* num_labels, void* stream) {
+    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && S > 0 && S <= CC_MAXS, "msm_ms_connected_components: S=%d must be in 1..%d", S, CC_MAXS);
     const size_t lds = sizeof(float) * (size_t)S * (MS_D + 1) + sizeof(int) * 2 * (size_t)S;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_batched_kernel, lds));
-    hipLaunchKernelGGL(ms_components_batched_kernel, dim3(M), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_connected_components_batched");
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_kernel, lds));
+    hipLaunchKernelGGL(ms_components_kernel, dim3(M), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
+    MSM_CHECK_LAUNCH("msm_ms_connected_components");
     return MSM_OK;
 }
 
-extern "C" int msm_ms_relabel_largest_zero_batched(int64_t* labels, int M, int n, const int64_t* counts, int num_labels,
-                                                   const int32_t* num_alive, void* stream) {
-    MSM_REQUIRE(labels && counts && M > 0 && M <= MSB_MAXM && n > 0 && num_labels > 0, "msm_ms_relabel_largest_zero_batched: bad arguments");
-    hipLaunchKernelGGL(ms_relabel_batched_kernel, dim3(min(2048, cdiv(n, 256)), M), dim3(256), 0, (hipStream_t)stream, labels, n, counts,
+extern "C" int msm_ms_relabel_largest_zero(int64_t* labels, int M, int n, const int64_t* counts, int num_labels,
+                                           const int32_t* num_alive, void* stream) {
+    MSM_REQUIRE(labels && counts && M > 0 && M <= MSB_MAXM && n > 0 && num_labels > 0, "msm_ms_relabel_largest_zero: bad arguments");
+    hipLaunchKernelGGL(ms_relabel_kernel, dim3(min(2048, cdiv(n, 256)), M), dim3(256), 0, (hipStream_t)stream, labels, n, counts,
                        num_labels, num_alive);
-    MSM_CHECK_LAUNCH("msm_ms_relabel_largest_zero_batched");
+    MSM_CHECK_LAUNCH("msm_ms_relabel_largest_zero");
     return MSM_OK;
 }

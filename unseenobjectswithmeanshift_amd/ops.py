@@ -1128,6 +1128,19 @@ def _check_xb(xb, n, d, who):
     return xb
 
 
+def _ms_select_seeds(X, num_seeds, first, first_index, stepwise, give_up_mask):
+    """X (M,n,64); ``first`` int64 (M,) on the device, or None with the host scalar ``first_index`` (one map: nothing is copied)."""
+    M, n, d = X.shape
+    seeds = torch.empty((M, num_seeds, d), device=X.device, dtype=torch.float32)
+    idx = torch.empty((M, num_seeds), device=X.device, dtype=torch.int64)
+    need = lib().msm_ms_seed_workspace(M, n)
+    ws = torch.empty((need,), device=X.device, dtype=torch.float32)
+    rc = lib().msm_ms_select_seeds(_p(X), M, n, d, num_seeds, _p(first), first_index, _p(seeds), _p(idx), _p(ws), need,
+                                   (1 if stepwise else 0) | (2 if give_up_mask else 0), give_up_mask, _stream())
+    check(rc, "msm_ms_select_seeds")
+    return seeds, idx
+
+
 def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=False, xb=None):
     """Farthest-point seeding.  X (n,64) unit rows.  Returns (seeds (S,64), indices int64 (S,)).  The single-launch
     persistent kernel (maps up to 393 216 rows) needs its workgroups co-resident; if other work holds the CUs it gives up
@@ -1137,20 +1150,18 @@ def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=Fal
     launch per step over the copy; distances are those of the rounded points, so the indices may differ from the fp32 path's."""
     _c(X, "X")
     n, d = X.shape
-    seeds = torch.empty((num_seeds, d), device=X.device, dtype=torch.float32)
-    idx = torch.empty((num_seeds,), device=X.device, dtype=torch.int64)
-    need = lib().msm_ms_seed_workspace(n)
-    ws = torch.empty((need,), device=X.device, dtype=torch.float32)
     if xb is not None and n > 393216:
         _check_xb(xb, n, d, "ms_select_seeds")
+        seeds = torch.empty((num_seeds, d), device=X.device, dtype=torch.float32)
+        idx = torch.empty((num_seeds,), device=X.device, dtype=torch.int64)
+        need = lib().msm_ms_seed_workspace(1, n)
+        ws = torch.empty((need,), device=X.device, dtype=torch.float32)
         rc = lib().msm_ms_select_seeds_bf16(_p(xb), _p(X), n, d, num_seeds, int(first_index), _p(seeds), _p(idx), _p(ws), need,
                                             (1 if stepwise else 0) | (2 if _test_give_up else 0), _stream())
         check(rc, "msm_ms_select_seeds_bf16")
         return seeds, idx
-    rc = lib().msm_ms_select_seeds(_p(X), n, d, num_seeds, int(first_index), _p(seeds), _p(idx), _p(ws), need,
-                                   (1 if stepwise else 0) | (2 if _test_give_up else 0), _stream())
-    check(rc, "msm_ms_select_seeds")
-    return seeds, idx
+    seeds, idx = _ms_select_seeds(X[None], num_seeds, None, int(first_index), stepwise, 1 if _test_give_up else 0)
+    return seeds[0], idx[0]
 
 
 def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None):
@@ -1160,6 +1171,8 @@ def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None):
     if precision not in ("f32", "f32_split", "bf16"):
         raise ValueError(f"ms_hill_climb: precision must be 'f32', 'f32_split' or 'bf16', not {precision!r}")
     _c(X, "X"), _c(Z, "Z")
+    if precision == "f32":
+        return ms_hill_climb_batched(X[None], Z[None], kappa, iters)[0]
     n, d = X.shape
     S = Z.shape[0]
     Z = Z.clone()
@@ -1169,47 +1182,33 @@ def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None):
         ws = torch.empty((need,), device=X.device, dtype=torch.float32)
         check(lib().msm_ms_hill_climb_bf16(_p(xb), n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()), "msm_ms_hill_climb_bf16")
         return Z
-    need = (lib().msm_ms_hill_climb_split_workspace if precision == "f32_split" else lib().msm_ms_hill_climb_workspace)(n, S)
+    need = lib().msm_ms_hill_climb_split_workspace(n, S)
     ws = torch.empty((need,), device=X.device, dtype=torch.float32)
-    fn = lib().msm_ms_hill_climb_split if precision == "f32_split" else lib().msm_ms_hill_climb
-    rc = fn(_p(X), n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream())
-    check(rc, "msm_ms_hill_climb_split" if precision == "f32_split" else "msm_ms_hill_climb")
+    check(lib().msm_ms_hill_climb_split(_p(X), n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()), "msm_ms_hill_climb_split")
     return Z
 
 
 def ms_assign(X, Z, seed_labels, num_labels):
     """labels[i] = seed_labels[first argmin_s 0.5(1 - X_i.Z_s)], counts = bincount(labels)."""
-    _c(X, "X"), _c(Z, "Z"), _c(seed_labels, "seed_labels", torch.int64)
-    n, d = X.shape
-    labels = torch.empty((n,), device=X.device, dtype=torch.int64)
-    counts = torch.empty((num_labels,), device=X.device, dtype=torch.int64)
-    rc = lib().msm_ms_assign(_p(X), n, d, _p(Z), Z.shape[0], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
-    check(rc, "msm_ms_assign")
-    return labels, counts
+    labels, counts = ms_assign_batched(X[None], Z[None], seed_labels[None], num_labels)
+    return labels[0], counts[0]
 
 
 def ms_connected_components(Z, epsilon):
     """mean_shift.py:41-76 on the device: Z (S,64) -> (seed_labels (S,) int64, num (2,) int32 = [labels that survive =
     len(unique(seed_labels)), labels created])."""
-    _c(Z, "Z")
-    S = Z.shape[0]
-    seed_labels = torch.empty((S,), device=Z.device, dtype=torch.int64)
-    num = torch.empty((2,), device=Z.device, dtype=torch.int32)
-    check(lib().msm_ms_connected_components(_p(Z), S, Z.shape[1], float(epsilon), _p(seed_labels), _p(num), _stream()),
-          "msm_ms_connected_components")
-    return seed_labels, num
+    seed_labels, num = ms_connected_components_batched(Z[None], epsilon)
+    return seed_labels[0], num[0]
 
 
 def ms_relabel_largest_zero(labels, counts, num_alive=None):
     """mean_shift.py:211-227 in place: label 0 <-> the first-argmax label of counts[:num], num = len(unique(seed_labels)) read from
-    the device tensor ``num_alive`` (ms_connected_components()[1]) when given, else every entry of counts."""
-    _c(labels, "labels", torch.int64), _c(counts, "counts", torch.int64), _c(num_alive, "num_alive", torch.int32)
-    rc = lib().msm_ms_relabel_largest_zero(_p(labels), labels.numel(), _p(counts), counts.numel(), _p(num_alive), _stream())
-    check(rc, "msm_ms_relabel_largest_zero")
+    the device tensor ``num_alive`` (ms_connected_components()[1], or its first element alone) when given, else every entry of counts."""
+    ms_relabel_largest_zero_batched(labels.view(1, -1), counts.view(1, -1), num_alive)
     return labels
 
 
-# ---- M maps of one size per call (msm_ms_*_batched; exact fp32 plan only: "f32_split" / "bf16" callers keep the per-map ops) ----
+# ---- M maps of one size per call (exact fp32 plan; the single-map ops above are their M = 1 views, "f32_split" / "bf16" are per map) ----
 def _first_indices_device(first_indices, M, n, device, who):
     """int64 (M,) device tensor of first seed indices.  A host sequence / array / tensor is range-checked here; a device tensor is
     taken as it is (no host synchronisation; the kernel clamps into the map)."""
@@ -1235,34 +1234,26 @@ def ms_select_seeds_batched(X, num_seeds, first_indices, stepwise=False, _test_g
     _c(X, "X")
     M, n, d = X.shape
     first = _first_indices_device(first_indices, M, n, X.device, "ms_select_seeds_batched")
-    seeds = torch.empty((M, num_seeds, d), device=X.device, dtype=torch.float32)
-    idx = torch.empty((M, num_seeds), device=X.device, dtype=torch.int64)
-    need = lib().msm_ms_seed_batched_workspace(M, n)
-    ws = torch.empty((need,), device=X.device, dtype=torch.float32)
     mask = 0
     for m in (_test_give_up or ()):
         if not 0 <= int(m) < min(M, 64):
             raise RuntimeError("ms_select_seeds_batched: _test_give_up names maps 0 .. min(M, 64) - 1")
         mask |= 1 << int(m)
-    rc = lib().msm_ms_select_seeds_batched(_p(X), M, n, d, num_seeds, _p(first), _p(seeds), _p(idx), _p(ws), need,
-                                           (1 if stepwise else 0) | (2 if mask else 0), mask, _stream())
-    check(rc, "msm_ms_select_seeds_batched")
-    return seeds, idx
+    return _ms_select_seeds(X, num_seeds, first, 0, stepwise, mask)
 
 
 def ms_hill_climb_batched(X, Z, kappa, iters):
-    """ms_hill_climb (precision "f32") for M maps: X (M,n,64), Z (M,S,64) -> the updated copy of Z, each map's bitwise equal to
-    ms_hill_climb(X[m], Z[m], kappa, iters) (same per-map grid, slab walk and summation order)."""
+    """ms_hill_climb (precision "f32") for M maps: X (M,n,64), Z (M,S,64) -> the updated copy of Z; a map's result does not depend
+    on its neighbours (same per-map grid, slab walk and summation order for every M)."""
     _c(X, "X"), _c(Z, "Z")
     M, n, d = X.shape
     if Z.dim() != 3 or Z.shape[0] != M or Z.shape[2] != d:
         raise RuntimeError(f"ms_hill_climb_batched: Z has shape {tuple(Z.shape)}, expected ({M}, S, {d})")
     S = Z.shape[1]
     Z = Z.clone()
-    need = lib().msm_ms_hill_climb_batched_workspace(M, n, S)
+    need = M * lib().msm_ms_hill_climb_workspace(n, S)
     ws = torch.empty((need,), device=X.device, dtype=torch.float32)
-    check(lib().msm_ms_hill_climb_batched(_p(X), M, n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()),
-          "msm_ms_hill_climb_batched")
+    check(lib().msm_ms_hill_climb(_p(X), M, n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()), "msm_ms_hill_climb")
     return Z
 
 
@@ -1274,8 +1265,8 @@ def ms_assign_batched(X, Z, seed_labels, num_labels):
         raise RuntimeError(f"ms_assign_batched: Z {tuple(Z.shape)} / seed_labels {tuple(seed_labels.shape)} do not match X {tuple(X.shape)}")
     labels = torch.empty((M, n), device=X.device, dtype=torch.int64)
     counts = torch.empty((M, num_labels), device=X.device, dtype=torch.int64)
-    rc = lib().msm_ms_assign_batched(_p(X), M, n, d, _p(Z), Z.shape[1], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
-    check(rc, "msm_ms_assign_batched")
+    rc = lib().msm_ms_assign(_p(X), M, n, d, _p(Z), Z.shape[1], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
+    check(rc, "msm_ms_assign")
     return labels, counts
 
 
@@ -1285,20 +1276,23 @@ def ms_connected_components_batched(Z, epsilon):
     M, S, d = Z.shape
     seed_labels = torch.empty((M, S), device=Z.device, dtype=torch.int64)
     num = torch.empty((M, 2), device=Z.device, dtype=torch.int32)
-    check(lib().msm_ms_connected_components_batched(_p(Z), M, S, d, float(epsilon), _p(seed_labels), _p(num), _stream()),
-          "msm_ms_connected_components_batched")
+    check(lib().msm_ms_connected_components(_p(Z), M, S, d, float(epsilon), _p(seed_labels), _p(num), _stream()),
+          "msm_ms_connected_components")
     return seed_labels, num
 
 
 def ms_relabel_largest_zero_batched(labels, counts, num_alive=None):
     """ms_relabel_largest_zero per map, in place: labels int64 (M,n), counts int64 (M,num_labels), num_alive int32 (M,2)
-    (ms_connected_components_batched()[1]) or None."""
+    (ms_connected_components_batched()[1]) or None.  Map m reads num_alive[m][0] only, so one map may pass that element alone."""
     _c(labels, "labels", torch.int64), _c(counts, "counts", torch.int64), _c(num_alive, "num_alive", torch.int32)
     M, n = labels.shape
-    if counts.dim() != 2 or counts.shape[0] != M or (num_alive is not None and tuple(num_alive.shape) != (M, 2)):
-        raise RuntimeError("ms_relabel_largest_zero_batched: counts must be (M, num_labels) and num_alive (M, 2)")
-    rc = lib().msm_ms_relabel_largest_zero_batched(_p(labels), M, n, _p(counts), counts.shape[1], _p(num_alive), _stream())
-    check(rc, "msm_ms_relabel_largest_zero_batched")
+    if counts.dim() != 2 or counts.shape[0] != M:
+        raise RuntimeError(f"ms_relabel_largest_zero_batched: counts has shape {tuple(counts.shape)}, expected ({M}, num_labels)")
+    if num_alive is not None and tuple(num_alive.shape) != (M, 2) and not (M == 1 and num_alive.numel() >= 1):
+        raise RuntimeError(f"ms_relabel_largest_zero_batched: num_alive has shape {tuple(num_alive.shape)}, expected ({M}, 2) "
+                           "(one map may pass its count alone: any tensor with at least one element)")
+    rc = lib().msm_ms_relabel_largest_zero(_p(labels), M, n, _p(counts), counts.shape[1], _p(num_alive), _stream())
+    check(rc, "msm_ms_relabel_largest_zero")
     return labels
 
 
