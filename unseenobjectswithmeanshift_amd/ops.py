@@ -54,7 +54,8 @@ def _c(t, name, dtype=torch.float32):
 # ----------------------------------------------------------------------------------------------
 def gemm(a, w, bias=None, *, a2=None, act=None, out=None, split_k=1):
     """out[..., n] = act((a + a2) @ w.T + bias) for row-major a (..., K) and w (N, K).
-    split_k > 1 returns raw partial sums of shape (split_k, ..., N) (bias/act must be None)."""
+    split_k > 1 returns raw partial sums of shape (split_k, ..., N) (bias/act must be None, and so must out).
+    out: an fp32 contiguous tensor of shape (..., N) on a's device to write into (a contiguous view at a storage offset is fine)."""
     _c(a, "a"), _c(w, "w"), _c(bias, "bias"), _c(a2, "a2")
     K = a.shape[-1]
     N = w.shape[0]
@@ -74,9 +75,15 @@ def gemm(a, w, bias=None, *, a2=None, act=None, out=None, split_k=1):
     if split_k > 1:
         if bias is not None or act is not None:
             raise RuntimeError("split_k output is raw: bias/act are applied by the consumer")
+        if out is not None:
+            raise RuntimeError("split_k allocates its (split_k, ..., N) parts itself: out must be None")
         out = torch.empty((split_k,) + tuple(lead) + (N,), device=a.device, dtype=torch.float32)
     elif out is None:
         out = torch.empty(tuple(lead) + (N,), device=a.device, dtype=torch.float32)
+    else:
+        _c(out, "out")
+        if out.device != a.device or tuple(out.shape) != tuple(lead) + (N,):
+            raise RuntimeError(f"out must be {tuple(lead) + (N,)} on {a.device}, got {tuple(out.shape)} on {out.device}")
     rc = lib().msm_gemm_f32(_p(a), _p(a2), _p(w), _p(bias), _p(out), Mb, N, K, batch,
                             K, 1, Mb * K, a2_sb, 0, N, 1, Mb * N, M * N,
                             0, 0, 0, 0, 1 if bias is not None else 0, 1 if act == "relu" else 0,
