@@ -1,6 +1,7 @@
 """Kernel-level parity: every C-ABI entry point against the CPU oracle / plain torch fp32 on the
 same seeded inputs.  Needs a real MI355X (pytest -m gpu)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -8,6 +9,10 @@ import torch
 import torch.nn.functional as F
 
 from oracle import msm_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import dec_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -649,7 +654,8 @@ def test_decoder_fused_tails(B, Q, prec):
     fp16 -- what is left is fp32 accumulation; that this form is closer to the exact chain than the bf16 one is
     test_decoder_tails_f16_is_closer_to_exact_than_bf16.  prec = "bf16x2" (round 6, what the "bf16" plan runs): hi + lo bf16 WEIGHT
     fragments beside the hi + lo activation split -- against the fp64 chain on the EXACT weights under the bf16 form's bound (what is
-    left is 2^-17 per operand)."""
+    left is 2^-17 per operand).  At 200, 7 and 48 rows every fp32 call here takes the 8-row tiles (TileF8); the 16-row fp32 kernels, the
+    other tile kinds and the row edges are tests/test_gpu_dec_tails.py's."""
     E, Fh = 256, 2048
     r = lambda *s, seed, k=1.0: (rnd(*s, seed=seed) * k)
     o, res, qpos = r(B, Q, E, seed=1), r(B, Q, E, seed=2), r(Q, E, seed=3)
@@ -671,16 +677,13 @@ def test_decoder_fused_tails(B, Q, prec):
     A = (lambda t: t.float().to(torch.float16).double()) if f16 else (lambda t: t)
     closed_ = globals()["closed"]
     closed = lambda got, ref, rtol, atol: closed_(got, ref, rtol=rtol * tol, atol=atol * tol + (4e-5 if f16 else 0.0))  # noqa: E731
-    # the documented fragment order (include/msm_hip.h)
-    N_, K_ = w_in.shape
-    frag = lambda m, dt: m.view(N_ // 16, 16, K_ // 64, 2, 2, 4, 4).permute(0, 2, 3, 5, 1, 4, 6).contiguous().view(N_ // 16, K_ // 64, 1024).to(dt)
-    if x2:              # per row tile: the K / 64 chunks of bf16(W), then the K / 64 chunks of bf16(W - bf16(W))
-        hi = w_in.to(torch.bfloat16)
-        want = torch.cat([frag(hi.float(), torch.bfloat16), frag(w_in - hi.float(), torch.bfloat16)], 1).reshape(N_, 2 * K_)
-    elif bf or f16:     # [t][kc][up][lq][lj][h][c] <- W[t*16 + lj][kc*64 + (2 up + h)*16 + lq*4 + c]
-        want = frag(w_in, torch.float16 if f16 else torch.bfloat16).reshape(N_, K_)
+    # the documented fragment order (include/msm_hip.h; restated once in tests/dec_cases.py)
+    if x2:
+        want = dec_cases.frag_bf16x2(w_in)
+    elif bf or f16:
+        want = dec_cases.frag_16(w_in, torch.float16 if f16 else torch.bfloat16)
     else:
-        want = w_in.view(N_ // 16, 16, K_ // 64, 4, 4, 4).permute(0, 2, 3, 4, 1, 5).contiguous().view(N_, K_)
+        want = dec_cases.frag_f32(w_in)
     assert torch.equal(pack(w_in).cpu(), want)
     wo, w_in = rw(wo), rw(w_in)                              # references below use the rounded weights; pack() rounds again (idempotent)
     # post_cross
