@@ -1,9 +1,17 @@
-"""ctypes binding of libmsm_hip.so (C ABI declared in include/msm_hip.h).
+"""ctypes binding of libmsm_hip.so, read from its C header.
+
+include/msm_hip.h is the only description of the C ABI: ``parse_header`` turns its prototypes into the ctypes signatures, its
+MSM_OPT_* enum into ``OPTIONS`` and its ``#define MSM_ABI_VERSION`` into ``ABI_VERSION``, once, when this module is imported.
+A new entry point is declared in the header, defined in csrc/ and announced by a bump of MSM_ABI_VERSION; there is no second
+place to edit.  Type rule: a parameter with a ``*`` is a ``c_void_p`` (device and host pointers alike), ``int`` / ``int64_t`` /
+``uint64_t`` / ``float`` by value are the ctypes type of that name, ``const char*`` is the one pointer return type
+(``c_char_p``); anything else in the header is an error, not a guess.
 
 The product path has no CPU fallback: if the shared library is missing or a call fails, a
 RuntimeError is raised (the reference silently falls back to a PyTorch path on ANY exception,
 ops/modules/ms_deform_attn.py:116-121 -- deliberately not reproduced).
 """
+import collections
 import ctypes
 import os
 import re
@@ -13,160 +21,101 @@ LIB_PATH = os.path.join(_HERE, "libmsm_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msm_hip.h")
 
 _lib = None
-ABI_VERSION = 30     # must equal MSM_ABI_VERSION of include/msm_hip.h (checked when the library is loaded)
 
-c_f = ctypes.c_void_p      # float* (device)
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_l = ctypes.c_int64
-c_fl = ctypes.c_float
+_BY_VALUE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
 
-_SIGNATURES = {
-    "msm_abi_version": (c_i, []),
-    "msm_last_error_string": (ctypes.c_char_p, []),
-    "msm_set_option": (c_i, [c_i, c_i]),
-    "msm_get_option": (c_i, [c_i]),
-    "msm_gemm_f32": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
-                           c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l,
-                           c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_layernorm_f32": (c_i, [c_f, c_f, c_i, c_l, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_p]),
-    "msm_groupnorm_stats_f32": (c_i, [c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_groupnorm_apply_f32": (c_i, [c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_groupnorm_apply_split": (c_i, [c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_groupnorm_apply_f16": (c_i, [c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_groupnorm_apply_nchw_f32": (c_i, [c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_groupnorm_nchw_pool_f32": (c_i, [c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),
-    "msm_pos_embed_sine": (c_i, [c_f, c_i, c_i, c_i, c_l, c_l, c_f, c_fl, c_fl, c_p]),
-    "msm_transpose_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_p]),
-    "msm_l2_normalize_nchw_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_msda_locations": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_l, c_i, c_i, c_i, c_p]),
-    "msm_mask_logits_fwd": (c_i, [c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_f, c_l, c_p]),
-    "msm_pool_mask_taps": (c_i, [c_f, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),
-    "msm_attn_mask_pooled": (c_i, [c_f, c_l, c_f, c_l, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_pack_mask_features_bf16": (c_i, [c_f, c_p, c_i, c_i, c_i, c_p]),
-    "msm_pack_mask_features_f16": (c_i, [c_f, c_p, c_i, c_i, c_i, c_p]),
-    "msm_mask_logits_bf16_fwd": (c_i, [c_f, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_f, c_l, c_p]),
-    "msm_pack_mask_features_split": (c_i, [c_f, c_p, c_i, c_i, c_i, c_p]),
-    "msm_mask_logits_split_fwd": (c_i, [c_f, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_f, c_l, c_p]),
-    "msm_hypersphere_attn_workspace": (c_l, [c_i, c_i, c_i, c_i]),
-    "msm_hypersphere_attn_fwd": (c_i, [c_f, c_f, c_f, c_p, c_p, c_f, c_i, c_i, c_i, c_i,
-                                       c_l, c_l, c_l, c_l, c_l, c_l, c_fl, c_f, c_l, c_p]),
-    "msm_hypersphere_attn_lp_fwd": (c_i, [c_f, c_p, c_p, c_i, c_p, c_p, c_f, c_i, c_i, c_i, c_i,
-                                          c_l, c_l, c_l, c_l, c_l, c_l, c_fl, c_f, c_l, c_p]),
-    "msm_hypersphere_attn_bwd_workspace": (c_l, [c_i, c_i, c_i]),
-    "msm_hypersphere_attn_bwd": (c_i, [c_f, c_f, c_f, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
-                                       c_l, c_l, c_l, c_l, c_l, c_l, c_fl, c_f, c_l, c_p]),
-    "msm_msdeform_attn_fwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_bwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_fwd_f64": (c_i, [c_f, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_bwd_f64": (c_i, [c_f, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_enc_fwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_encoder_block_stream_floats": (c_l, [c_i, c_i]),
-    "msm_value_to_head_major_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_enc_hm_fwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msda_pack_proj": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_enc_fused_fwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_encoder_block_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_encoder_block_split_stream_bytes": (c_l, [c_i, c_i]),
-    "msm_encoder_block_split_fwd": (c_i, [c_f, c_f, c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_encoder_block_lp_stream_bytes": (c_l, [c_i, c_i]),
-    "msm_encoder_block_lp_fwd": (c_i, [c_f, c_f, c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_encoder_block_hm_stream_bytes": (c_l, [c_i, c_i]),
-    "msm_encoder_block_hm_small_floats": (c_i, [c_i]),
-    "msm_encoder_block_hm_fwd": (c_i, [c_p, c_f, c_p, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_msdeform_attn_enc_lp_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_msdeform_attn_enc_lp_fused_fwd": (c_i, [c_p, c_p, c_p, c_f, c_f, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_f32_to_f16": (c_i, [c_f, c_p, c_l, c_p]),
-    "msm_bias_act_nhwc": (c_i, [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p]),
-    "msm_nhwc_to_nchw_f32": (c_i, [c_p, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_ucn_embedding_tail": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_f32_to_f16_rows": (c_i, [c_f, c_p, c_i, c_l, c_l, c_p]),
-    "msm_kv_project_f32": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_l, c_i, c_p]),
-    "msm_kv_project_multi_f32": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
-    "msm_kv_project_multi_bf16": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_kv_project_multi_split": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
-    "msm_tokens_proj_nchw_f32": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_i, c_fl, c_i, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_dec_pack_weight": (c_i, [c_f, c_f, c_i, c_i, c_p]),
-    "msm_dec_post_cross": (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_post_self": (c_i, [c_f] * 9 + [c_i, c_f, c_f, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_heads": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_i] + [c_f] * 15 + [c_p, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_pack_weight_bf16": (c_i, [c_f, c_p, c_i, c_i, c_p]),
-    "msm_dec_post_cross_bf16": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_f] + [c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_post_self_bf16": (c_i, [c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_p] + [c_i, c_f, c_f, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_heads_bf16": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_f] + [c_f] * 4 +
-                           [c_p, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_nchw_to_tokens_f16": (c_i, [c_f, c_p, c_i, c_i, c_i, c_p]),
-    "msm_mask_conv3x3_folded": (c_i, [c_p, c_f, c_l, c_l, c_p, c_p, c_i, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_attn_pack_kv_weights": (c_i, [c_f, c_p, c_i, c_p]),
-    "msm_attn_mask_bits_bytes": (c_l, [c_i, c_i, c_i]),
-    "msm_attn_pack_mask_bits": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
-    "msm_hypersphere_attn_fused_kv_fwd": (c_i, [c_f, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_fl, c_f, c_l, c_p]),
-    "msm_dec_pack_weight_f16": (c_i, [c_f, c_p, c_i, c_i, c_p]),
-    "msm_dec_post_cross_f16": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_f] + [c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_post_self_f16": (c_i, [c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_p] + [c_i, c_f, c_f, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_heads_f16": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_f] + [c_f] * 4 +
-                          [c_p, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_heads_mask": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_f] + [c_f] * 4 +
-                           [c_f, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_pack_weight_bf16x2": (c_i, [c_f, c_p, c_i, c_i, c_p]),
-    "msm_dec_post_cross_bf16x2": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_f] + [c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_post_self_bf16x2": (c_i, [c_f, c_f, c_p, c_f, c_f, c_f, c_p, c_f, c_p] + [c_i, c_f, c_f, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_dec_heads_bf16x2": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_p, c_f, c_f] + [c_f] * 4 +
-                             [c_p, c_i, c_i, c_i, c_fl, c_p]),
-    "msm_l2_prefetch": (c_i, [c_p, c_p, c_i, c_p]),
-    "msm_dec_set_prefetch": (c_i, [c_p, c_p, c_i]),
-    "msm_ms_seed_workspace": (c_l, [c_i, c_i]),
-    "msm_ms_select_seeds": (c_i, [c_f, c_i, c_i, c_i, c_i, c_p, c_l, c_f, c_p, c_f, c_l, c_i, ctypes.c_uint64, c_p]),
-    "msm_ms_hill_climb_workspace": (c_l, [c_i, c_i]),
-    "msm_ms_hill_climb": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
-    "msm_ms_hill_climb_split_workspace": (c_l, [c_i, c_i]),
-    "msm_ms_hill_climb_split": (c_i, [c_f, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
-    "msm_ms_bf16_rows": (c_l, [c_i]),
-    "msm_ms_pack_bf16": (c_i, [c_f, c_i, c_i, c_p, c_p]),
-    "msm_ms_select_seeds_bf16": (c_i, [c_p, c_f, c_i, c_i, c_i, c_l, c_f, c_p, c_f, c_l, c_i, c_p]),
-    "msm_ms_hill_climb_bf16": (c_i, [c_p, c_i, c_i, c_f, c_i, c_fl, c_i, c_f, c_l, c_p]),
-    "msm_ms_assign": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_i, c_p]),
-    "msm_ms_connected_components": (c_i, [c_f, c_i, c_i, c_i, c_fl, c_p, c_p, c_p]),
-    "msm_ms_relabel_largest_zero": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_p]),
-    "msm_topk_class_scores": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]),
-    "msm_topk_class_scores_gather": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_l, c_i, c_f, c_p]),
-    "msm_conv1x1_in_f32": (c_i, [c_f, c_f, c_f, c_f, c_l, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv1x1_in_multi_f32": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_i, c_i, c_p]),
-    "msm_conv1x1_in_multi_lp": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_i, c_i, c_p]),
-    "msm_conv1x1_in_multi_wide": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_i, c_i, c_p]),
-    "msm_conv1x1_in_lp": (c_i, [c_f, c_p, c_f, c_f, c_l, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_f32": (c_i, [c_f, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_bf16": (c_i, [c_f, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_f16": (c_i, [c_f, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_f16h": (c_i, [c_p, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_nchw_f16": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_split": (c_i, [c_f, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_nchw_f32": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_conv3x3_c64_nchw_bf16": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_encoder_prologue_stream_floats": (c_l, [c_i]),
-    "msm_encoder_prologue_fwd": (c_i, [c_f, c_p, c_f, c_p, c_i, c_i, c_fl, c_f, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_encoder_prologue_hm_weight_bytes": (c_l, []),
-    "msm_encoder_prologue_hm_fwd": (c_i, [c_f, c_p, c_f, c_p, c_i, c_i, c_fl, c_p, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_p]),
-    "msm_label_stats": (c_i, [c_f, c_f, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "msm_label_image": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_crop_resize": (c_i, [c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_paste_labels": (c_i, [c_f, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_p]),
-    "msm_mask_nms_workspace": (c_l, [c_i, c_i, c_i, c_i]),
-    "msm_mask_nms": (c_i, [c_f, c_f, c_p, c_fl, c_f, c_f, c_f, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
-    "msm_ingest_frames": (c_i, [c_p, c_p, c_i, c_fl, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_instance_postprocess_workspace": (c_l, [c_i, c_i, c_i, c_i]),
-    "msm_eval_counts_workspace": (c_l, [c_i]),
-    "msm_eval_counts": (c_i, [c_f, c_f, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "msm_match_cost": (c_i, [c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                             c_fl, c_fl, c_fl, c_p]),
-    "msm_point_loss_workspace": (c_l, [c_i, c_i]),
-    "msm_point_loss_fwd": (c_i, [c_p, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                 c_i, c_i, c_i, c_fl, c_p]),
-    "msm_point_loss_bwd": (c_i, [c_p, c_p, c_p, c_f, c_f, c_p, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                 c_i, c_i, c_i, c_fl, c_i, c_p]),
-    "msm_instance_postprocess": (c_i, [c_f, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
-    "msm_instance_postprocess_resized": (c_i, [c_f, c_p, c_f, c_f, c_f, c_f] + [c_i] * 11 + [c_f, c_p]),
-}
+Header = collections.namedtuple("Header", "signatures params options abi_version opt_auto")
+
+
+def _tokens(decl):
+    """'const float*const* w' -> ['const', 'float', '*', 'const', '*', 'w']"""
+    return decl.replace("*", " * ").split()
+
+
+def _define(text, name):
+    m = re.findall(r"^[ \t]*#[ \t]*define[ \t]+%s[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$" % name, text, flags=re.M)
+    if len(m) != 1:
+        raise ValueError(f"msm_hip.h: expected one integer `#define {name}`, found {len(m)}")
+    return int(m[0])
+
+
+def _options(body):
+    """Names of the MSM_OPT_* enumerators (without prefix and COUNT); set_option passes the position as the key, so values
+    must be the implicit 0, 1, 2, ..."""
+    names = []
+    items = [e.strip() for e in body.split(",")]
+    for i, item in enumerate(items[:-1] if items[-1] == "" else items):
+        m = re.fullmatch(r"MSM_OPT_(\w+)(?:\s*=\s*(.+))?", item, flags=re.S)
+        if not m:
+            raise ValueError(f"msm_hip.h: cannot read enumerator `{item}`")
+        if m.group(2) is not None and (i, m.group(2).strip()) != (0, "0"):
+            raise ValueError(f"msm_hip.h: enumerator `{item}` sets a value; option keys are positions, only `= 0` on the first is allowed")
+        names.append(m.group(1))
+    if not names or names[-1] != "COUNT" or "COUNT" in names[:-1] or len(set(names)) != len(names):
+        raise ValueError("msm_hip.h: the MSM_OPT_* enum must hold distinct names and end with MSM_OPT_COUNT")
+    return tuple(names[:-1])
+
+
+def _prototype(stmt):
+    m = re.fullmatch(r"([\w\s*]+?)\b(\w+)\s*\(([^(){}]*)\)", stmt)
+    if not m:
+        raise ValueError(f"msm_hip.h: not a function prototype: `{stmt}`")
+    ret, name, plist = " ".join(_tokens(m.group(1))), m.group(2), m.group(3).strip()
+    if ret != "const char *" and ret not in _BY_VALUE:
+        raise ValueError(f"msm_hip.h: {name}: no ctypes rule for the return type `{ret}`")
+    restype = _BY_VALUE.get(ret, ctypes.c_char_p)
+    argtypes, names = [], []
+    for p in ([] if plist in ("", "void") else plist.split(",")):
+        *typ, pname = [t for t in _tokens(p) if t != "const"] or [""]
+        typ = " ".join(typ)
+        if not typ or not re.fullmatch(r"[A-Za-z_]\w*", pname):
+            raise ValueError(f"msm_hip.h: {name}: parameter `{' '.join(p.split())}` needs a type and a plain name")
+        if "*" not in typ and typ not in _BY_VALUE:
+            raise ValueError(f"msm_hip.h: {name}: no ctypes rule for the by-value type `{typ}` of `{pname}`")
+        argtypes.append(_BY_VALUE.get(typ, ctypes.c_void_p))
+        names.append(pname)
+    return name, (restype, argtypes), names
+
+
+def parse_header(text):
+    """The C ABI as include/msm_hip.h declares it: Header(signatures {name: (restype, [argtypes])} and params {name: [parameter
+    names]} in declaration order, options (MSM_OPT_* names in enum order), abi_version, opt_auto).  Strict: every statement of
+    the header must be understood, a ValueError names the one that is not."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    abi_version, opt_auto = _define(text, "MSM_ABI_VERSION"), _define(text, "MSM_OPT_AUTO")
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", " ", text, flags=re.M)
+    text, wrappers = re.subn(r'\bextern\s*"C"\s*\{', " ", text)
+    enums = re.findall(r"\benum\s*\{([^{}]*)\}\s*;", text)
+    if len(enums) != 1:
+        raise ValueError(f"msm_hip.h: expected one anonymous enum (MSM_OPT_*), found {len(enums)}")
+    text = re.sub(r"\benum\s*\{[^{}]*\}\s*;", " ", text)
+    *stmts, tail = text.split(";")
+    if "".join(tail.split()) != "}" * wrappers:
+        raise ValueError(f"msm_hip.h: unterminated statement at the end: `{' '.join(tail.split())}`")
+    signatures, params = {}, {}
+    for stmt in stmts:
+        name, sig, names = _prototype(" ".join(stmt.split()))
+        if name in signatures:
+            raise ValueError(f"msm_hip.h: {name} is declared twice")
+        signatures[name], params[name] = sig, names
+    return Header(signatures, params, _options(enums[0]), abi_version, opt_auto)
+
+
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes bindings of libmsm_hip.so are read from it. "
+                           "Keep include/ next to the package directory.")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+_HEADER = _load_header()            # once per process
+_SIGNATURES = _HEADER.signatures
+ABI_VERSION = _HEADER.abi_version   # lib() checks it against msm_abi_version() of the loaded library (a stale build)
+# kernel-selection overrides, for tools/ and tests/ only: position in OPTIONS = value of MSM_OPT_<name>
+OPTIONS = _HEADER.options
+OPT_AUTO = _HEADER.opt_auto
 
 
 def declared_symbols():
@@ -196,13 +145,6 @@ def lib():
     return _lib
 
 
-# kernel-selection overrides of include/msm_hip.h (enum order), for tools/ and tests/ only
-OPTIONS = ("MASK_NC", "MASKB_TARGET", "GEMM_TILE", "GEMM_SHALLOW", "ATTN_TARGET", "ATTN_KERNEL", "ATTN_QK_MAX", "ATTN_QKCFG",
-           "CONVIN_NT", "POST_GENERIC", "ENC_NO_COOP", "MSDA_GENERIC", "MS_CHUNK", "MS_NO_PERSISTENT", "ATTN_FUSED_KV", "KV_PIPE", "MASK_KERNEL",
-           "MS_SPLIT_KERNEL", "CONV3_WIDE", "DEC_TILE32", "POST_RESIZE_DIRECT", "GN_POOL")
-OPT_AUTO = -1
-
-
 def set_option(name, value=OPT_AUTO):
     """msm_set_option(MSM_OPT_<name>, value); value OPT_AUTO restores the library's own choice.  Returns the old value."""
     key = OPTIONS.index(name)
@@ -215,7 +157,7 @@ def set_option(name, value=OPT_AUTO):
 
 
 class option:
-    """``with option("MASK_NC", 1): ...`` -- scoped override, restored on exit."""
+    """``with option(name, value): ...`` (name: one of OPTIONS) -- scoped override, restored on exit."""
 
     def __init__(self, name, value):
         self.name, self.value = name, value
@@ -239,12 +181,15 @@ class CallTimer:
         self.records = []
         self._saved = {}
 
+    @staticmethod
+    def timed_entry_points():
+        """The launch entry points: the functions whose last parameter is the stream."""
+        return [name for name, names in _HEADER.params.items() if names[-1:] == ["stream"]]
+
     def __enter__(self):
         import torch
         L = lib()
-        for name, (_, args) in _SIGNATURES.items():
-            if not args or args[-1] is not c_p or name.endswith("_workspace"):
-                continue
+        for name in self.timed_entry_points():
             fn = getattr(L, name)
             self._saved[name] = fn
 
