@@ -254,6 +254,13 @@ class MeanShiftMaskFormer(PlanAttributes, nn.Module):
                                                         padded_size=padded_size, output_size=output_size)
         return scores, classes, masks, boxes, qidx
 
+    def input_spec(self):
+        """What this model's own ``forward`` applies to "image" in front of ``inference_images`` -> (mean or None, std or None,
+        size divisibility): (x - mean) / std with the (C,1,1) buffers, then zeros at the right / bottom up to a multiple of the
+        divisibility.  "depth" is never normalised and is padded like the image (_forward_images).  A caller that feeds
+        ``inference_images`` directly (two_stage.BatchedTwoStage) applies exactly this."""
+        return self.pixel_mean, self.pixel_std, max(int(self.size_divisibility), 1)
+
     def _image_features(self, inputs):
         return self.backbone(inputs["image"], inputs["depth"]) if "depth" in inputs else self.backbone(inputs["image"])
 
@@ -381,6 +388,10 @@ class PretrainedMeanShiftMaskFormer(MeanShiftMaskFormer):
     def forward(self, batched_inputs):
         """See MeanShiftMaskFormer._forward_images; "depth" follows "image" (same size, same padding, PM:275, 286); no normalisation."""
         return self._forward_images(batched_inputs, ("image", "depth") if self.use_depth else ("image",), lambda v: v)
+
+    def input_spec(self):
+        """No normalisation, whatever the constructor was given: this meta-arch's ``forward`` applies none."""
+        return None, None, max(int(self.size_divisibility), 1)
 
     def _image_features(self, inputs):
         """The RGB-D front of ``inference_images`` on padded inputs {"image": (B,3,Hp,Wp)[, "depth": xyz (B,3,Hp,Wp)]}: the two towers

@@ -1631,6 +1631,47 @@ def ingest_frames(color, depth, cam, lut, *, depth_div=1000.0, swap_rb=False, fr
     return image, xyz
 
 
+def prepare_inputs(image, depth=None, *, mean=None, std=None, frame=None, out_image=None, out_depth=None):
+    """What a meta-arch applies in front of the network, in one launch (msm_prepare_inputs): image (N,C,H,W) -> ((image - mean[c]) /
+    std[c], or the same bits without ``mean`` / ``std`` (C values each, on the device)) padded with zeros at the right / bottom to
+    ``frame`` = (Hp, Wp) (default (H, W)); depth (N,Cd,H,W) or None is copied bit for bit into the same frame -> (image_out
+    (N,C,Hp,Wp), depth_out (N,Cd,Hp,Wp) or None).  ``out_image`` / ``out_depth`` are written in place when given (e.g. the static
+    inputs of a graph slot); an output cannot be its own input."""
+    _c(image, "image"), _c(depth, "depth"), _c(mean, "mean"), _c(std, "std")
+    if image.dim() != 4:
+        raise RuntimeError(f"prepare_inputs: image {tuple(image.shape)} must be (N, C, H, W)")
+    N, C, H, W = image.shape
+    Hp, Wp = (H, W) if frame is None else (int(frame[0]), int(frame[1]))
+    dev = image.device
+    if (mean is None) != (std is None):
+        raise RuntimeError("prepare_inputs: mean and std go together")
+    for t, name in ((mean, "mean"), (std, "std")):
+        if t is not None and (t.numel() != C or t.device != dev):
+            raise RuntimeError(f"prepare_inputs: {name} {tuple(t.shape)} on {t.device} must hold {C} values on {dev}")
+    Cd = 0
+    if depth is not None:
+        if depth.dim() != 4 or depth.shape[0] != N or tuple(depth.shape[2:]) != (H, W) or depth.device != dev:
+            raise RuntimeError(f"prepare_inputs: depth {tuple(depth.shape)} on {depth.device} must be ({N}, Cd, {H}, {W}) on {dev}")
+        Cd = depth.shape[1]
+    elif out_depth is not None:
+        raise RuntimeError("prepare_inputs: out_depth without depth")
+    outs = []
+    for t, name, ch in ((out_image, "out_image", C), (out_depth, "out_depth", Cd)):
+        if t is None:
+            t = torch.empty((N, ch, Hp, Wp), device=dev, dtype=torch.float32) if ch else None
+        else:
+            _c(t, name)
+            if tuple(t.shape) != (N, ch, Hp, Wp) or t.device != dev:
+                raise RuntimeError(f"prepare_inputs: {name} {tuple(t.shape)} on {t.device} must be {(N, ch, Hp, Wp)} on {dev}")
+        outs.append(t)
+    image_out, depth_out = outs
+    if N == 0:                                    # (an empty tensor has no address to hand over)
+        return image_out, depth_out
+    check(lib().msm_prepare_inputs(_p(image), _p(depth), _p(mean), _p(std), _p(image_out), _p(depth_out), N, C, Cd, H, W, Hp, Wp,
+                                   _stream()), "msm_prepare_inputs")
+    return image_out, depth_out
+
+
 # ----------------------------------------------------------------------------------------------
 # backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------

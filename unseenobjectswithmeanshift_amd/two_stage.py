@@ -33,6 +33,8 @@ the oracle.  Differences from the reference, on purpose:
     raise; it also fixes what numpy's default argsort leaves open: equal scores are visited higher index first, equal areas are
     numbered in the order they were kept.
 """
+import collections
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -726,6 +728,48 @@ def test_batch_crop(samples, predictor, predictor_crop=None, *, use_depth=True, 
 # configs[3] as a replayable pipeline: both stages from captured HIP graphs, the two device -> host transfers of a batch
 # overlapped with the other batch in flight.
 # ----------------------------------------------------------------------------------------------------------------------
+class LRUBuckets:
+    """A dict in least-recently-used order with a cap: ``put`` of a new key into a full table first evicts the least recently used
+    entry and hands it to ``on_evict(key, value)``; ``get`` of a present key makes it the most recent.  ``cap=None`` never evicts.
+    Host-only bookkeeping (the crop buckets of a BatchedTwoStage slot: the callback waits for the slot's stream before the entry's
+    graph and buffers are dropped)."""
+
+    def __init__(self, cap=None, on_evict=None):
+        if cap is not None and int(cap) < 1:
+            raise ValueError(f"the cap must be at least 1 (or None for no cap), got {cap}")
+        self.cap = None if cap is None else int(cap)
+        self.on_evict = on_evict
+        self._d = collections.OrderedDict()
+
+    def get(self, key, default=None):
+        if key not in self._d:
+            return default
+        self._d.move_to_end(key)
+        return self._d[key]
+
+    def put(self, key, value):
+        if key in self._d:
+            self._d.move_to_end(key)
+        else:
+            while self.cap is not None and len(self._d) >= self.cap:
+                old, gone = self._d.popitem(last=False)
+                if self.on_evict is not None:
+                    self.on_evict(old, gone)
+                del gone
+        self._d[key] = value
+        return value
+
+    def keys(self):
+        """Least recently used first."""
+        return list(self._d)
+
+    def __contains__(self, key):
+        return key in self._d
+
+    def __len__(self):
+        return len(self._d)
+
+
 class BatchedTwoStage:
     """test_batch_crop_nolabel (lib/fcn/test_utils.py:339-421 per frame) for batches of ``frames`` frames of one
     size, with the model called directly (``model.inference_images``: backbone + head + post-processing) and both stages replayed
@@ -752,12 +796,25 @@ class BatchedTwoStage:
     ``count`` (F,) are reachable as ``pipeline.extras`` from the moment ``consume`` is called for a batch (tensors owned by the slot,
     valid until its next batch); ``run`` without a consumer clones them, one dict per batch, into ``pipeline.batch_extras``.
 
-    The captured graphs follow the model's execution plan: a plan switch (set_precision, ...) or a parameter update re-captures
-    (graphs.StaleCheck)."""
+    The captured graphs follow the models' execution plans: a plan switch (set_precision, ...) or a parameter update of either model
+    re-captures (graphs.StaleCheck, one per model).
+
+    ``model_crop``: the second stage's own network (the reference's predictor_crop, test_utils.py:339-421: the published weights come
+    as pairs); None = ``model``.  Both stages apply what their model's own ``forward`` applies in front of ``inference_images``
+    (``model.input_spec()``: (x - pixel_mean) / pixel_std, zero padding of image and depth to the size divisibility, ``padded_size``)
+    in ONE launch inside the stage's graph (ops.prepare_inputs, _prepared) -- the first stage on the frames, the second on the crops at
+    ``crop_size`` -- and nothing at all for a model that neither normalises nor needs padding.  The slot's ``images`` / ``depths``
+    stay the unpadded, un-normalised frames: the crops are cut from them (crop_rois, test_dataset.py:62-112), and every result is at
+    the frame size.
+
+    ``max_buckets=n``: a slot keeps at most n captured crop buckets; one more evicts the least recently replayed one (graph, table,
+    host buffers, outputs, workspaces) after the slot's stream has been synchronised.  ``max_crops=m``: a batch with more than m ROIs
+    captures nothing; its second stage runs eagerly on the slot's stream in unpadded chunks of at most m crops (the eager batch's
+    ``crop_batch``).  None (the defaults) = no cap."""
 
     def __init__(self, model, frames, size, *, use_depth=True, topk=False, confident_score=0.7, low_threshold=0.4, num_class=2,
                  depth_threshold=0.5, bucket=16, crop_size=CROP_SIZE, slots=2, graphs=True, order="bgr", depth_scale=1000.0,
-                 use_nms=False, nms_thresh=0.7):
+                 use_nms=False, nms_thresh=0.7, model_crop=None, max_buckets=None, max_crops=None):
         from .graphs import StaleCheck, _slot_stream
         self.use_nms, self.nms_thresh = bool(use_nms), float(nms_thresh)
         self.extras, self.batch_extras = None, []
@@ -770,10 +827,18 @@ class BatchedTwoStage:
         self.kw = dict(topk=topk, confident_score=confident_score, low_threshold=low_threshold, num_class=num_class)
         self.depth_threshold = float(depth_threshold)
         self.bucket, self.crop_size, self.use_graphs = int(bucket), int(crop_size), bool(graphs)
+        self.model_crop = model if model_crop is None else model_crop
         self._sig = StaleCheck(model)
+        self._sig_crop = self._sig if self.model_crop is model else StaleCheck(self.model_crop)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("BatchedTwoStage needs the model on the GPU (there is no CPU path)")
+        if next(self.model_crop.parameters()).device != dev:
+            raise ValueError(f"model_crop is on {next(self.model_crop.parameters()).device}, model on {dev}: both stages run on one device")
+        if max_buckets is not None and int(max_buckets) < 1 or max_crops is not None and int(max_crops) < 1:
+            raise ValueError(f"max_buckets / max_crops must be at least 1 (or None for no cap), got {max_buckets} / {max_crops}")
+        self.max_buckets = None if max_buckets is None else int(max_buckets)
+        self.max_crops = None if max_crops is None else int(max_crops)
         self.dev = dev
         self._slots = [self._new_slot(_slot_stream(dev, i)) for i in range(max(1, int(slots)))]
 
@@ -782,18 +847,45 @@ class BatchedTwoStage:
         Fr, H, W, dev = self.frames, self.H, self.W, self.dev
         k = int(LABEL_BINS)
         with torch.cuda.stream(stream):
-            st = dict(stream=stream, sig=None, g1=None, g2={}, label=None, s2={}, nms_ws=None, extras=None,
+            st = dict(stream=stream, sig=None, g1=None, label=None, s2=self._new_buckets(stream), cur=None, nms_ws=None, prep=None, extras=None,
                       images=torch.zeros((Fr, 3, H, W), device=dev), depths=torch.zeros((Fr, 3, H, W), device=dev) if self.use_depth else None,
                       thr=torch.full((Fr, 1), self.depth_threshold, device=dev), thr_host=[self.depth_threshold] * Fr,
                       host_stats=torch.zeros(Fr * k * 5 + Fr, dtype=torch.int32).pin_memory(),
                       ev1=torch.cuda.Event(), ev2=torch.cuda.Event(), rows=None, n=0, nb=0)
         return st
 
-    def _predict(self, images, depths):
-        inputs = {"image": images}
-        if depths is not None:
-            inputs["depth"] = depths
-        sc, cl, mk = self.model.inference_images(inputs, tuple(int(v) for v in images.shape[-2:]))[:3]
+    def _new_buckets(self, stream):
+        """The crop buckets of a slot: crop count -> dict(g (the graph), refs, table, table_host, host_keys, out, nms_ws, prep).  An
+        evicted bucket is dropped only after the slot's stream has run dry: no graph goes while it may still be running."""
+        return LRUBuckets(self.max_buckets, lambda nb, b: stream.synchronize())
+
+    def _prepared(self, owner, model, images, depths):
+        """What ``model.forward`` applies in front of ``inference_images`` (model.input_spec()) -> (image, depth, image_size,
+        padded_size or None).  A model that neither normalises nor needs padding at this size gets the tensors as they are: nothing
+        is allocated, nothing is launched.  Otherwise ONE launch (ops.prepare_inputs) writes buffers that live in ``owner`` (the
+        slot, or the slot's crop bucket, like nms_ws) so that a captured graph keeps writing the memory it was captured with."""
+        spec = getattr(model, "input_spec", None)
+        mean, std, div = (None, None, 1) if spec is None else spec()      # (any module with an inference_images of its own: as it is)
+        H, W = (int(v) for v in images.shape[-2:])
+        frame = (-(-H // div) * div, -(-W // div) * div)
+        if mean is None and frame == (H, W):
+            return images, depths, (H, W), None
+        from . import ops
+        bufs = owner.get("prep")
+        if bufs is None:
+            bufs = owner["prep"] = {}
+        key = (tuple(images.shape), None if depths is None else tuple(depths.shape), frame)
+        if key not in bufs:
+            bufs[key] = tuple(None if t is None else torch.empty(tuple(t.shape[:2]) + frame, device=self.dev) for t in (images, depths))
+        image, depth = ops.prepare_inputs(images, depths, mean=mean, std=std, frame=frame, out_image=bufs[key][0], out_depth=bufs[key][1])
+        return image, depth, (H, W), frame
+
+    def _predict(self, owner, model, images, depths):
+        image, depth, size, padded = self._prepared(owner, model, images, depths)
+        inputs = {"image": image}
+        if depth is not None:
+            inputs["depth"] = depth
+        sc, cl, mk = (model.inference_images(inputs, size) if padded is None else model.inference_images(inputs, size, padded))[:3]
         return sc, cl, mk
 
     def _labels(self, owner, sc, cl, mk):
@@ -809,7 +901,7 @@ class BatchedTwoStage:
         return lab, dict(out_score=score, bbox=bbox, count=count)
 
     def _stage1(self, st):
-        sc, cl, mk = self._predict(st["images"], st["depths"])
+        sc, cl, mk = self._predict(st, self.model, st["images"], st["depths"])
         lab, st["extras"] = self._labels(st, sc, cl, mk)
         if st["depths"] is not None:
             lab = filter_labels_depth(lab, st["depths"], st["thr"])
@@ -817,22 +909,30 @@ class BatchedTwoStage:
         st["host_stats"].copy_(torch.cat([stats.reshape(-1), overflow]), non_blocking=True)          # the batch's first transfer
         return lab
 
-    def _stage2(self, st, nb):
+    def _stage2(self, st, b, chunk=None):
+        """The second stage on the crops of bucket ``b``'s table, as one batch (the captured form) or, eagerly, ``chunk`` crops at a time
+        through the network (_batch_crop's loop): everything around the network sees all the crops at once either way."""
         from . import ops
-        b = st["s2"][nb]
         rgb, msk, dep = ops.crop_resize(st["images"], st["depths"], st["label"], b["table"], self.crop_size)
-        sc, cl, mk = self._predict(rgb, dep)
-        labels_crop, _ = self._labels(b, sc, cl, mk)
+        if chunk is None:
+            sc, cl, mk = self._predict(b, self.model_crop, rgb, dep)
+            labels_crop, _ = self._labels(b, sc, cl, mk)
+        else:
+            labels_crop = torch.empty((rgb.shape[0], self.crop_size, self.crop_size), device=self.dev)
+            for c0 in range(0, rgb.shape[0], chunk):
+                sc, cl, mk = self._predict(b, self.model_crop, rgb[c0:c0 + chunk], None if dep is None else dep[c0:c0 + chunk])
+                labels_crop[c0:c0 + chunk] = self._labels(b, sc, cl, mk)[0]
         raw = labels_crop.clone()
         area, bad, lab, keys = _match_pre(labels_crop, msk, dep)
         if keys is not None:
             b["host_keys"].copy_(keys, non_blocking=True)                                             # the batch's second transfer
         return dict(rgb_crop=rgb, mask_crop=msk, depth_crop=dep, labels_crop=raw, area=area, bad=bad, lab=lab)
 
-    def _capture(self, st, fn, *args):
-        """Run fn twice (weight caches, MIOpen's solver choices), then capture it on the slot's stream."""
+    def _capture(self, st, model, fn, *args):
+        """Run fn twice (weight caches, MIOpen's solver choices), then capture it on the slot's stream -> (graph, fn's outputs, the
+        cache references of ``model``, the one whose stage fn is)."""
         if not self.use_graphs:
-            return None, fn(st, *args)
+            return None, fn(st, *args), None
         for _ in range(2):
             fn(st, *args)
         st["stream"].synchronize()
@@ -840,8 +940,7 @@ class BatchedTwoStage:
         with torch.cuda.graph(g, stream=st["stream"]):
             out = fn(st, *args)
         from .graphs import cache_refs
-        st["refs"].append(cache_refs(self.model))              # the derived tensors the graph reads by address stay alive with it
-        return g, out
+        return g, out, cache_refs(model)                       # the derived tensors the graph reads by address stay alive with it
 
     def _ingest_raw(self, st, samples):
         """A batch of raw camera frames into the slot's static inputs (on the slot's stream): host frames go through the slot's pinned
@@ -885,9 +984,10 @@ class BatchedTwoStage:
             raise ValueError(f"BatchedTwoStage was built for {self.frames} frames, got {len(samples)}")
         raw = _raw_batch(samples)
         sig = self._sig()
-        if st["sig"] != sig:                                   # first use, plan switch or parameter update: re-capture everything
+        sig = (sig, sig if self._sig_crop is self._sig else self._sig_crop())
+        if st["sig"] != sig:                                   # first use, plan switch or parameter update of either model: re-capture everything
             st["stream"].synchronize()
-            st.update(sig=sig, g1=None, g2={}, s2={}, label=None, refs=[], nms_ws=None, extras=None)
+            st.update(sig=sig, g1=None, s2=self._new_buckets(st["stream"]), cur=None, label=None, refs=None, nms_ws=None, prep=None, extras=None)
         with torch.cuda.stream(st["stream"]):
             st["stream"].wait_stream(torch.cuda.current_stream())
             if raw:
@@ -902,7 +1002,7 @@ class BatchedTwoStage:
                     st["thr"].copy_(torch.tensor(thr, dtype=torch.float32)[:, None])
                     st["thr_host"] = thr
             if st["label"] is None:
-                st["g1"], st["label"] = self._capture(st, self._stage1)
+                st["g1"], st["label"], st["refs"] = self._capture(st, self.model, self._stage1)
                 if st["g1"] is not None:
                     st["g1"].replay()
             elif st["g1"] is not None:
@@ -920,24 +1020,30 @@ class BatchedTwoStage:
         st["rows"], st["n"] = rows, len(rows)
         if not rows:
             return
-        nb = -(-len(rows) // self.bucket) * self.bucket
+        eager = self.max_crops is not None and len(rows) > self.max_crops
+        nb = len(rows) if eager else -(-len(rows) // self.bucket) * self.bucket
         st["nb"] = nb
         with torch.cuda.stream(st["stream"]):
-            if nb not in st["s2"]:
-                st["s2"][nb] = dict(table=torch.zeros((nb, 8), dtype=torch.int32, device=self.dev),
-                                    table_host=torch.zeros((nb, 8), dtype=torch.int32).pin_memory(),
-                                    host_keys=torch.zeros(nb, dtype=torch.float64).pin_memory(), out=None)
-            b = st["s2"][nb]
+            b = None if eager else st["s2"].get(nb)            # (a hit makes the bucket the most recently replayed one)
+            if b is None:
+                b = dict(table=torch.zeros((nb, 8), dtype=torch.int32, device=self.dev),
+                         table_host=torch.zeros((nb, 8), dtype=torch.int32).pin_memory(),
+                         host_keys=torch.zeros(nb, dtype=torch.float64).pin_memory(), out=None, g=None, refs=None)
+                if not eager:
+                    st["s2"].put(nb, b)                        # one bucket more than max_buckets: the least recently replayed one goes first
+            st["cur"] = b
             b["table_host"].copy_(torch.tensor(rows + [rows[0]] * (nb - len(rows)), dtype=torch.int32))
             b["table"].copy_(b["table_host"], non_blocking=True)
-            if b["out"] is None:
-                st["g2"][nb], b["out"] = self._capture(st, self._stage2, nb)
-                if st["g2"][nb] is not None:
-                    st["g2"][nb].replay()
-            elif st["g2"][nb] is not None:
-                st["g2"][nb].replay()
+            if eager:                                          # more crops than max_crops: no bucket, no graph; chunks of max_crops, unpadded
+                b["out"] = self._stage2(st, b, self.max_crops)
+            elif b["out"] is None:
+                b["g"], b["out"], b["refs"] = self._capture(st, self.model_crop, self._stage2, b)
+                if b["g"] is not None:
+                    b["g"].replay()
+            elif b["g"] is not None:
+                b["g"].replay()
             else:
-                b["out"] = self._stage2(st, nb)
+                b["out"] = self._stage2(st, b)
             st["ev2"].record(st["stream"])
 
     @torch.no_grad()
@@ -948,7 +1054,7 @@ class BatchedTwoStage:
         if n == 0:
             return label, torch.zeros_like(label), rows
         st["ev2"].synchronize()
-        b = st["s2"][st["nb"]]
+        b = st["cur"]
         o = b["out"]
         if self.use_depth:
             keys = b["host_keys"].numpy()[:n].tolist()
