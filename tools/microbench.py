@@ -358,30 +358,50 @@ def cfg5():
 
 
 def meanshift():
-    """Classic UCN clustering at 640x480 (n = 307200, S = 100, 10 iterations) and the cfg-5 stress size."""
+    """Classic UCN clustering: 640x480 (n = 307200, S = 100, 10 iterations), 16 crops of 224x224 in one batched call and, for the
+    cosine metric, the cfg-5 stress size.  ``--metric cosine|euclidean|both`` (default cosine) picks the entry points; the
+    Euclidean inputs are the same planted clusters without the normalisation."""
+    import argparse
     from unseenobjectswithmeanshift_amd import mean_shift as ms
     from unseenobjectswithmeanshift_amd import synthetic as syn
-    for n, S, iters, k in ((307200, 100, 10, 12), (1228800, 300, 20, 24)):
-        X, _ = syn.synth_unit_embeddings(n, 64, clusters=k, sigma=0.15, seed=3)
-        Xd = X.to(DEV)
-        t_seed = timeit(lambda: ops.ms_select_seeds(Xd, S, 7), iters=3, warm=1)
-        seeds, _ = ops.ms_select_seeds(Xd, S, 7)
-        t_hill = timeit(lambda: ops.ms_hill_climb(Xd, seeds, 20.0, iters), iters=3, warm=1)
-        Z = ops.ms_hill_climb(Xd, seeds, 20.0, iters)
-        lab = torch.zeros(S, dtype=torch.int64, device=DEV)
-        t_asg = timeit(lambda: ops.ms_assign(Xd, Z, lab, 1), iters=3, warm=1)
-        for _ in range(2):                      # warm-up: host BLAS threads, allocator
-            ms.mean_shift_smart_init(Xd, 20.0, S, iters, first_index=7)
-        torch.cuda.synchronize()
-        reps = 10 if n < 500000 else 3
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            labels, sel = ms.mean_shift_smart_init(Xd, 20.0, S, iters, first_index=7)
-        torch.cuda.synchronize()
-        t_all = (time.perf_counter() - t0) / reps
-        print(f"mean-shift n={n} S={S} it={iters}: seeding {t_seed / 1e3:7.2f} ms ({S * n * 256 / t_seed / 1e6:6.2f} TB/s), "
-              f"hill-climb {t_hill / 1e3:7.2f} ms ({4.0 * S * n * 64 * iters / t_hill / 1e6:6.1f} TFLOP/s), assign {t_asg / 1e3:6.2f} ms, "
-              f"end-to-end {t_all * 1e3:7.2f} ms = {1 / t_all:6.1f} images/s, clusters={int(labels.max()) + 1}", flush=True)
+    ap = argparse.ArgumentParser(prog="microbench.py meanshift")
+    ap.add_argument("--metric", choices=("cosine", "euclidean", "both"), default="cosine")
+    args = ap.parse_args(sys.argv[2:])
+    metrics = ("cosine", "euclidean") if args.metric == "both" else (args.metric,)
+    for M, n, S, iters, k in ((1, 307200, 100, 10, 12), (16, 50176, 100, 10, 6), (1, 1228800, 300, 20, 24)):
+        X, ids = syn.synth_unit_embeddings(n, 64, clusters=k, sigma=0.15, seed=3)
+        for metric in metrics:
+            if metric == "euclidean" and n > 393216:
+                continue                             # the stress size is the bf16 plan's: cosine only
+            Xm = X if metric == "cosine" else X * (1.0 + 0.25 * torch.sin(torch.arange(n, dtype=torch.float32))[:, None])
+            Xd = Xm.to(DEV)[None].repeat(M, 1, 1).contiguous()
+            first = [(7 + 1009 * m) % n for m in range(M)]
+            kw = dict(metric=metric)
+            t_seed = timeit(lambda: ops.ms_select_seeds_batched(Xd, S, first, **kw), iters=3, warm=1)
+            seeds, _ = ops.ms_select_seeds_batched(Xd, S, first, **kw)
+            t_hill = timeit(lambda: ops.ms_hill_climb_batched(Xd, seeds, 20.0, iters, **kw), iters=3, warm=1)
+            Z = ops.ms_hill_climb_batched(Xd, seeds, 20.0, iters, **kw)
+            t_cc = timeit(lambda: ops.ms_connected_components_batched(Z, 0.04, **kw), iters=3, warm=1)
+            lab = torch.zeros((M, S), dtype=torch.int64, device=DEV)
+            t_asg = timeit(lambda: ops.ms_assign_batched(Xd, Z, lab, 1, **kw), iters=3, warm=1)
+
+            def whole():
+                if M == 1:
+                    return ms.mean_shift_smart_init(Xd[0], 20.0, S, iters, first_index=first[0], **kw)
+                return ms.mean_shift_smart_init_batched(Xd, 20.0, S, iters, first_indices=first, **kw)
+            for _ in range(2):                      # warm-up: host BLAS threads, allocator
+                whole()
+            torch.cuda.synchronize()
+            reps = 10 if n < 500000 else 3
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                labels, sel = whole()
+            torch.cuda.synchronize()
+            t_all = (time.perf_counter() - t0) / reps
+            print(f"mean-shift {metric:9s} M={M} n={n} S={S} it={iters}: seeding {t_seed / 1e3:7.2f} ms ({M * S * n * 256 / t_seed / 1e6:6.2f} TB/s), "
+                  f"hill-climb {t_hill / 1e3:7.2f} ms ({4.0 * M * S * n * 64 * iters / t_hill / 1e6:6.1f} TFLOP/s), merge {t_cc / 1e3:6.3f} ms, "
+                  f"assign {t_asg / 1e3:6.2f} ms, end-to-end {t_all * 1e3:7.2f} ms = {M / t_all:6.1f} maps/s, clusters={int(labels.max()) + 1}",
+                  flush=True)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,10 @@
 //               turns a 16-point block into exp() weights in registers, already in A-operand
 //               layout for the W X product;
 //   assignment: one more X pass, S^T tiles + an in-register first-min argmin.
+//
+// The Euclidean metric (the `metric == 'euclidean'` branches of the same functions; msm_ms_*_l2) is the `L2` instantiation of the
+// stepwise seeding, hill climb, finish, merge and assignment bodies: d = ||x - z||_2, W = exp(-kappa d^2), Z <- W X / max(sum W, 1),
+// exact fp32 plan only.  The persistent seeding kernels and the split / bf16 climbs are cosine-only.
 #include "bf16.h"
 #include "common.h"
 #include <cstdlib>
@@ -42,7 +46,9 @@ __device__ __forceinline__ unsigned int ordered_bits(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <bool SMALL>
+// L2 (the Euclidean metric, MS:159-184): nearest[i] = min(nearest[i], ||X[i] - X[winner]||_2) from the DIFFERENCES -- the lane's four
+// (x - s)^2 terms, the same butterfly, then sqrtf.  The pass is an HBM stream, so the form is free, and it has no cancellation.
+template <bool SMALL, bool L2 = false>
 __device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, int n, unsigned long long* __restrict__ keys, int step,
                                                   float* __restrict__ nearest) {
     __shared__ float4 seed4[16];
@@ -83,8 +89,16 @@ __device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, i
             if (step > 1) near = nearest[min(gb + j, n - 1)];
         }
         float p[16];
+        if constexpr (L2) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) p[i] = x[i].x * s.x + x[i].y * s.y + x[i].z * s.z + x[i].w * s.w;
+            for (int i = 0; i < 16; ++i) {
+                const float dx = x[i].x - s.x, dy = x[i].y - s.y, dz = x[i].z - s.z, dw = x[i].w - s.w;
+                p[i] = dx * dx + dy * dy + dz * dz + dw * dw;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) p[i] = x[i].x * s.x + x[i].y * s.y + x[i].z * s.z + x[i].w * s.w;
+        }
         const float near_now = near;
         const int row = gb + j;
         // halving butterfly: after the stage with mask m, lanes with (j & m) keep the upper half of the rows
@@ -116,7 +130,7 @@ __device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, i
             p[0] = keep + wave_xor_dpp1(send);
         }
         if (row < n) {
-            const float d = fminf(near_now, 0.5f * (1.0f - p[0]));
+            const float d = fminf(near_now, L2 ? sqrtf(p[0]) : 0.5f * (1.0f - p[0]));
             nearest[row] = d;
             const unsigned long long key = ((unsigned long long)ordered_bits(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)row);
             best = key > best ? key : best;
@@ -136,12 +150,12 @@ __device__ __forceinline__ void ms_seed_step_body(const float* __restrict__ X, i
 
 // The step for M maps of one size in one launch: map = blockIdx.y, X [M][n][64], keys [M][key_stride], nearest [M][n].  A map's
 // workgroups run ms_seed_step_body on the map's own pointers, so its keys do not depend on M.
-template <bool SMALL>
+template <bool SMALL, bool L2 = false>
 __global__ __launch_bounds__(256) void ms_seed_step_kernel(const float* __restrict__ X, int n,
                                                            unsigned long long* __restrict__ keys, int key_stride, int step,
                                                            float* __restrict__ nearest) {
     const int64_t m = blockIdx.y;
-    ms_seed_step_body<SMALL>(X + m * n * MS_D, n, keys + m * key_stride, step, nearest + m * n);
+    ms_seed_step_body<SMALL, L2>(X + m * n * MS_D, n, keys + m * key_stride, step, nearest + m * n);
 }
 
 // ---- the same step on a bf16 copy of X (precision "bf16": BASELINE configs[4], n = 1 228 800, 300 seeds) ------------------------
@@ -652,13 +666,20 @@ __device__ __forceinline__ void stage_points(const float* __restrict__ X, int n,
 }
 
 // ---- hill climbing: part[wg] = sum over the workgroup's points of exp(kappa s) x ----------------
-template <int NSB>
+// L2 (the Euclidean metric, MS:21-24, 101-105): W = exp(-kappa ||z - x||^2) on the same score tile through the expansion
+// ||x||^2 + ||z||^2 - 2 x.z, clamped at 0 (the reference's distance is a norm: no weight exceeds 1).  The row norms live in the
+// first pad float of the LDS rows: ||z||^2 is summed when zs is staged, ||x||^2 from the float4 pieces a lane already holds when
+// it stages the slab, reduced over the 16 lanes of a row.  The update divides by clamp(sum_x W, min = 1) instead of normalising,
+// so the workgroup's partial carries one more column: part[wg] = [NSB*16][64] sums of W x, then [NSB*16] sums of W (lane (lj, lq)
+// owns seed sb*16 + lj for its four points; reduced over lq, then over the waves in the order of `accum`).
+template <int NSB, bool L2 = false>
 __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n, const float* __restrict__ Z, int S, float kappa,
                                              float* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* zs = lds;                          // [NSB*16][SZ]
     float* xsa = lds + NSB * 16 * SZ;         // [4 waves][16][SZ]
     float* accum = lds;                       // [NSB*16][64] cross-wave reduction, reuses zs after the loop
+    float* wacc = lds + NSB * 16 * MS_D;      // L2: [NSB*16] sums of W, behind accum (inside the old zs)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lj = lane & 15, lq = lane >> 4;
     for (int i = tid; i < NSB * 16 * MS_D; i += 256) {
@@ -666,7 +687,19 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
         zs[s * SZ + d] = (s < S) ? Z[(int64_t)s * MS_D + d] : 0.f;
     }
     __syncthreads();
+    if constexpr (L2) {
+        for (int s = tid; s < NSB * 16; s += 256) {
+            float q = 0.f;
+#pragma unroll 16
+            for (int k = 0; k < MS_D; ++k) q = fmaf(zs[s * SZ + k], zs[s * SZ + k], q);
+            zs[s * SZ + MS_D] = q;
+        }
+        __syncthreads();
+    }
     float* xs = xsa + wave * 16 * SZ;
+    float wsum[NSB];                          // L2 only
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) wsum[sb] = 0.f;
 
     f32x4 zn[NSB][4];
 #pragma unroll
@@ -675,6 +708,7 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
         for (int db = 0; db < 4; ++db) zn[sb][db] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const float kl2 = kappa * 1.4426950408889634f;
+    const float ke = L2 ? -kl2 : kl2;         // exponent scale: exp(kappa x.z), or exp(-kappa d^2)
     const int nblocks = (n + 15) / 16;
     // register-staged prefetch: the next 16 points are in flight while this slab's 32*NSB MFMAs run
     const int srow = lane >> 4, scol = (lane & 15) * 4;
@@ -691,12 +725,41 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
         *reinterpret_cast<float4*>(xs + (4 + srow) * SZ + scol) = nx1;
         *reinterpret_cast<float4*>(xs + (8 + srow) * SZ + scol) = nx2;
         *reinterpret_cast<float4*>(xs + (12 + srow) * SZ + scol) = nx3;
+        if constexpr (L2) {
+            // ||x||^2 of rows srow, 4 + srow, 8 + srow, 12 + srow: this lane's four columns, then the row's 16 lanes
+            float q0 = nx0.x * nx0.x + nx0.y * nx0.y + nx0.z * nx0.z + nx0.w * nx0.w;
+            float q1 = nx1.x * nx1.x + nx1.y * nx1.y + nx1.z * nx1.z + nx1.w * nx1.w;
+            float q2 = nx2.x * nx2.x + nx2.y * nx2.y + nx2.z * nx2.z + nx2.w * nx2.w;
+            float q3 = nx3.x * nx3.x + nx3.y * nx3.y + nx3.z * nx3.z + nx3.w * nx3.w;
+            q0 += wave_xor_dpp8(q0); q1 += wave_xor_dpp8(q1); q2 += wave_xor_dpp8(q2); q3 += wave_xor_dpp8(q3);
+            q0 += wave_xor_dpp4(q0); q1 += wave_xor_dpp4(q1); q2 += wave_xor_dpp4(q2); q3 += wave_xor_dpp4(q3);
+            q0 += wave_xor_dpp2(q0); q1 += wave_xor_dpp2(q1); q2 += wave_xor_dpp2(q2); q3 += wave_xor_dpp2(q3);
+            q0 += wave_xor_dpp1(q0); q1 += wave_xor_dpp1(q1); q2 += wave_xor_dpp1(q2); q3 += wave_xor_dpp1(q3);
+            if ((lane & 15) == 0) {
+                xs[srow * SZ + MS_D] = q0;
+                xs[(4 + srow) * SZ + MS_D] = q1;
+                xs[(8 + srow) * SZ + MS_D] = q2;
+                xs[(12 + srow) * SZ + MS_D] = q3;
+            }
+        }
         MS_LOAD_SLAB((pb + (int)gridDim.x * 4) * 16)
         // the slab is private to this wave; a wave-level fence orders the LDS writes before the reads
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         f32x4 st[NSB];
         score_block<NSB>(xs, zs, lj, lq, st);
+        if constexpr (L2) {
+            // st <- max(||x||^2 + ||z||^2 - 2 x.z, 0), the squared distance
+            float xx[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xx[r] = xs[(lq * 4 + r) * SZ + MS_D];
+#pragma unroll
+            for (int sb = 0; sb < NSB; ++sb) {
+                const float zz = zs[(sb * 16 + lj) * SZ + MS_D];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[sb][r] = fmaxf((xx[r] + zz) - 2.0f * st[sb][r], 0.f);
+            }
+        }
         // B operand of W X: X[point lq*4 + r][d = db*16 + lj]
         float xb[4][4];
 #pragma unroll
@@ -710,7 +773,8 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
             for (int sb = 0; sb < NSB; ++sb) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float w = __builtin_amdgcn_exp2f(kl2 * st[sb][r]);
+                    const float w = __builtin_amdgcn_exp2f(ke * st[sb][r]);
+                    if constexpr (L2) wsum[sb] += w;
 #pragma unroll
                     for (int db = 0; db < 4; ++db) zn[sb][db] = mfma16(w, xb[r][db], zn[sb][db]);
                 }
@@ -720,7 +784,8 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
             for (int sb = 0; sb < NSB; ++sb) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float w = (p0 + lq * 4 + r < n) ? __builtin_amdgcn_exp2f(kl2 * st[sb][r]) : 0.f;
+                    const float w = (p0 + lq * 4 + r < n) ? __builtin_amdgcn_exp2f(ke * st[sb][r]) : 0.f;
+                    if constexpr (L2) wsum[sb] += w;
 #pragma unroll
                     for (int db = 0; db < 4; ++db) zn[sb][db] = mfma16(w, xb[r][db], zn[sb][db]);
                 }
@@ -730,7 +795,7 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
     }
     // deterministic cross-wave reduction: waves add into `accum` one after another
     __syncthreads();   // every wave is done reading zs
-    for (int i = tid; i < NSB * 16 * MS_D; i += 256) accum[i] = 0.f;
+    for (int i = tid; i < NSB * 16 * (L2 ? MS_D + 1 : MS_D); i += 256) accum[i] = 0.f;      // L2: wacc follows accum
     __syncthreads();
     for (int w = 0; w < 4; ++w) {
         if (wave == w) {
@@ -740,23 +805,33 @@ __device__ __forceinline__ void ms_hill_body(const float* __restrict__ X, int n,
                 for (int db = 0; db < 4; ++db)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) accum[(sb * 16 + lq * 4 + r) * MS_D + db * 16 + lj] += zn[sb][db][r];
+            if constexpr (L2) {
+#pragma unroll
+                for (int sb = 0; sb < NSB; ++sb) {
+                    float v = wsum[sb];                      // the four lq of seed sb*16 + lj: (0 + 1) + (2 + 3) on every lane
+                    v += __shfl_xor(v, 16, 64);
+                    v += __shfl_xor(v, 32, 64);
+                    if (lq == 0) wacc[sb * 16 + lj] += v;
+                }
+            }
         }
         __syncthreads();
     }
-    float* dst = part + (int64_t)blockIdx.x * (NSB * 16 * MS_D);
-    for (int i = tid; i < NSB * 16 * MS_D; i += 256) dst[i] = accum[i];
+    constexpr int PW = L2 ? MS_D + 1 : MS_D;      // floats per seed row of the partial
+    float* dst = part + (int64_t)blockIdx.x * (NSB * 16 * PW);
+    for (int i = tid; i < NSB * 16 * PW; i += 256) dst[i] = accum[i];
 }
 
 #undef MS_LOAD_SLAB
 
 // M maps of one size: map = blockIdx.y, the per-map grid (gridDim.x) and slab walk do not depend on M, so neither do a map's
 // partials nor, after ms_hill_finish_kernel, its Z.  Z and part advance by z_stride / part_stride floats per map.
-template <int NSB>
+template <int NSB, bool L2 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void ms_hill_kernel(const float* __restrict__ X, int n,
                                                       const float* __restrict__ Z, int64_t z_stride, int S, float kappa,
                                                       float* __restrict__ part, int64_t part_stride) {
     const int64_t m = blockIdx.y;
-    ms_hill_body<NSB>(X + m * n * MS_D, n, Z + m * z_stride, S, kappa, part + m * part_stride);
+    ms_hill_body<NSB, L2>(X + m * n * MS_D, n, Z + m * z_stride, S, kappa, part + m * part_stride);
 }
 
 // ---- the same step with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split) -----------------------------
@@ -1301,13 +1376,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // Z[s] = normalize(sum_wg part[wg][s])  (MS:103 F.normalize).  16 waves per seed: wave w adds its fixed slice of
 // the workgroup partials (8 loads in flight), then the slices are added in wave order -- deterministic.
+// L2: Z[s] = (sum_wg part[wg][s]) / max(sum_wg wsum[wg][s], 1)  (MS:101-105); a workgroup's partial is [rows_padded][64] sums of
+// W x followed by [rows_padded] sums of W, which every lane of a wave adds up in the same slices and the same order.
+template <bool L2>
 __device__ __forceinline__ void ms_hill_finish_body(const float* __restrict__ part, int nwg, int rows_padded, float* __restrict__ Z) {
     __shared__ float slice[16][MS_D];
+    __shared__ float slice_w[16];
     const int s = blockIdx.x, d = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int per = (nwg + 15) / 16;
     const int g0 = w * per, g1 = min(nwg, g0 + per);
     const float* src = part + (int64_t)s * MS_D + d;
-    const int64_t stride = (int64_t)rows_padded * MS_D;
+    const int64_t stride = (int64_t)rows_padded * (L2 ? MS_D + 1 : MS_D);
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int g = g0;
     for (; g + 8 <= g1; g += 8) {
@@ -1316,21 +1395,40 @@ __device__ __forceinline__ void ms_hill_finish_body(const float* __restrict__ pa
     }
     for (; g < g1; ++g) a[0] += src[(int64_t)g * stride];
     slice[w][d] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    if constexpr (L2) {
+        const float* srcw = part + (int64_t)rows_padded * MS_D + s;
+        float b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        g = g0;
+        for (; g + 8 <= g1; g += 8) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) b[u] += srcw[(int64_t)(g + u) * stride];
+        }
+        for (; g < g1; ++g) b[0] += srcw[(int64_t)g * stride];
+        if (d == 0) slice_w[w] = ((b[0] + b[1]) + (b[2] + b[3])) + ((b[4] + b[5]) + (b[6] + b[7]));
+    }
     __syncthreads();
     if (w == 0) {
         float acc = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc += slice[i][d];
-        const float nrm = fmaxf(sqrtf(wave_sum(acc * acc)), 1e-12f);
-        Z[(int64_t)s * MS_D + d] = acc / nrm;
+        if constexpr (L2) {
+            float sw = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sw += slice_w[i];
+            Z[(int64_t)s * MS_D + d] = acc / fmaxf(sw, 1.0f);
+        } else {
+            const float nrm = fmaxf(sqrtf(wave_sum(acc * acc)), 1e-12f);
+            Z[(int64_t)s * MS_D + d] = acc / nrm;
+        }
     }
 }
 
 // map = blockIdx.y (the single-map split / planes / bf16 climbs: one map, strides 0)
+template <bool L2 = false>
 __global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __restrict__ part, int64_t part_stride, int nwg,
                                                               int rows_padded, float* __restrict__ Z, int64_t z_stride) {
     const int64_t m = blockIdx.y;
-    ms_hill_finish_body(part + m * part_stride, nwg, rows_padded, Z + m * z_stride);
+    ms_hill_finish_body<L2>(part + m * part_stride, nwg, rows_padded, Z + m * z_stride);
 }
 
 // ---- connected components of the converged seeds ------------------------------------------------------------------
@@ -1341,7 +1439,9 @@ __global__ __launch_bounds__(1024) void ms_hill_finish_kernel(const float* __res
 // lane and chunk, the mode is an LDS histogram + a wave reduction.  What this buys is not the arithmetic (a dozen steps of
 // a microsecond) but the HOST: the loop used to run there on a copy of the seeds, i.e. a device synchronisation and a
 // transfer in the middle of every clustering, with the GPU idle behind it.
+// L2 (the Euclidean metric, MS:58-60): the membership test is ||z_j - z_i||_2 <= eps, from the differences.
 constexpr int CC_MAXS = MS_SB * 16;
+template <bool L2>
 __device__ __forceinline__ void ms_components_body(const float* __restrict__ Z, int S, float eps, int64_t* __restrict__ labels_out,
                                                    int32_t* __restrict__ num_out) {
     extern __shared__ __attribute__((aligned(16))) float cz[];           // [S][MS_D + 1], then int lab[S], cnt[S]
@@ -1366,9 +1466,18 @@ __device__ __forceinline__ void ms_components_body(const float* __restrict__ Z, 
             comp[c] = false;
             if (j < S) {
                 float dot = 0.f;
+                if constexpr (L2) {
 #pragma unroll 16
-                for (int k = 0; k < MS_D; ++k) dot = fmaf(cz[j * ZS + k], cz[i * ZS + k], dot);
-                comp[c] = 0.5f * (1.0f - dot) <= eps;
+                    for (int k = 0; k < MS_D; ++k) {
+                        const float df = cz[j * ZS + k] - cz[i * ZS + k];
+                        dot = fmaf(df, df, dot);
+                    }
+                    comp[c] = sqrtf(dot) <= eps;
+                } else {
+#pragma unroll 16
+                    for (int k = 0; k < MS_D; ++k) dot = fmaf(cz[j * ZS + k], cz[i * ZS + k], dot);
+                    comp[c] = 0.5f * (1.0f - dot) <= eps;
+                }
                 if (comp[c] && lab[j] >= 0) {
                     atomicAdd(&cnt[lab[j]], 1);
                     labelled = true;
@@ -1414,13 +1523,17 @@ __device__ __forceinline__ void ms_components_body(const float* __restrict__ Z, 
 }
 
 // one wave per map: Z [M][S][64], labels_out [M][S], num_out [M][2]
+template <bool L2 = false>
 __global__ __launch_bounds__(64) void ms_components_kernel(const float* __restrict__ Z, int S, float eps,
                                                            int64_t* __restrict__ labels_out, int32_t* __restrict__ num_out) {
     const int64_t m = blockIdx.x;
-    ms_components_body(Z + m * S * MS_D, S, eps, labels_out + m * S, num_out + 2 * m);
+    ms_components_body<L2>(Z + m * S * MS_D, S, eps, labels_out + m * S, num_out + 2 * m);
 }
 
 // ---- assignment -----------------------------------------------------------------------------------
+// L2 (the Euclidean metric, MS:207-215): first argmin_s of ||z_s||^2 - 2 x.z_s on the same score tile -- ||x||^2 is constant
+// per point and sqrt is monotone; ||z_s||^2 sits in the first pad float of the seed's LDS row.
+template <bool L2>
 __device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int n, const float* __restrict__ Z, int S, int nchunks,
                                                const int64_t* __restrict__ seed_labels, int64_t* __restrict__ labels_out,
                                                unsigned long long* __restrict__ counts, int num_labels) {
@@ -1437,6 +1550,15 @@ __device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int 
     }
     for (int i = tid; i < num_labels; i += 256) hist[i] = 0u;
     __syncthreads();
+    if constexpr (L2) {
+        for (int s = tid; s < rows; s += 256) {
+            float q = 0.f;
+#pragma unroll 16
+            for (int k = 0; k < MS_D; ++k) q = fmaf(zs[s * SZ + k], zs[s * SZ + k], q);
+            zs[s * SZ + MS_D] = q;
+        }
+        __syncthreads();
+    }
     float* xs = xsa + wave * 16 * SZ;
     const int nblocks = (n + 15) / 16;
     for (int pb = blockIdx.x * 4 + wave; pb < nblocks; pb += gridDim.x * 4) {
@@ -1453,9 +1575,11 @@ __device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int 
 #pragma unroll
             for (int sb = 0; sb < MS_CH; ++sb) {
                 const int seed = (c * MS_CH + sb) * 16 + lj;
+                float zz = 0.f;
+                if constexpr (L2) zz = zs[seed * SZ + MS_D];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float dist = 0.5f * (1.0f - st[sb][r]);
+                    const float dist = L2 ? zz - 2.0f * st[sb][r] : 0.5f * (1.0f - st[sb][r]);
                     if (seed < S && dist < bd[r]) { bd[r] = dist; bi[r] = seed; }
                 }
             }
@@ -1483,12 +1607,13 @@ __device__ __forceinline__ void ms_assign_body(const float* __restrict__ X, int 
 }
 
 // map = blockIdx.y: X [M][n][64], Z [M][S][64], seed_labels [M][S], labels_out [M][n], counts [M][num_labels]
+template <bool L2 = false>
 __global__ __launch_bounds__(256) void ms_assign_kernel(const float* __restrict__ X, int n, const float* __restrict__ Z, int S,
                                                         int nchunks, const int64_t* __restrict__ seed_labels,
                                                         int64_t* __restrict__ labels_out,
                                                         unsigned long long* __restrict__ counts, int num_labels) {
     const int64_t m = blockIdx.y;
-    ms_assign_body(X + m * n * MS_D, n, Z + m * S * MS_D, S, nchunks, seed_labels + m * S, labels_out + m * n, counts + m * num_labels,
+    ms_assign_body<L2>(X + m * n * MS_D, n, Z + m * S * MS_D, S, nchunks, seed_labels + m * S, labels_out + m * n, counts + m * num_labels,
                    num_labels);
 }
 
@@ -1565,9 +1690,11 @@ static SeedWorkspace seed_workspace(float* ws, int M) {
 // The hill climb's walk over chunks of seed blocks, for M maps whose Z / partial sums lie z_stride / part_stride floats apart.
 // Per iteration: every chunk's partial sums ([G][nb * 16][64] per map, issued by `launch(Zc, Sc, nb, ws)`; all chunks of one
 // iteration read the same Z), then the finish launches.
-template <class Launch>
+// L2: the Euclidean form, whose partial rows carry the sum of the weights as a 65th float.
+template <bool L2 = false, class Launch>
 static int hill_iterations(float* Z, int M, int64_t z_stride, int S, int iters, float* parts, int64_t part_stride, int G, hipStream_t st,
                            Launch launch) {
+    constexpr int PW = L2 ? MS_D + 1 : MS_D;
     const int nsb = cdiv(S, 16);
     const int CH = hill_chunk(nsb);
     for (int it = 0; it < iters; ++it) {
@@ -1576,15 +1703,15 @@ static int hill_iterations(float* Z, int M, int64_t z_stride, int S, int iters, 
             const int nb = min(CH, nsb - b0);
             const int rc = launch(Z + (int64_t)b0 * 16 * MS_D, min(S - b0 * 16, nb * 16), nb, ws);
             if (rc != MSM_OK) return rc;
-            ws += (int64_t)G * nb * 16 * MS_D;
+            ws += (int64_t)G * nb * 16 * PW;
         }
         ws = parts;
         for (int b0 = 0; b0 < nsb; b0 += CH) {
             const int nb = min(CH, nsb - b0);
             const int Sc = min(S - b0 * 16, nb * 16);
-            hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(Sc, M), dim3(1024), 0, st, ws, part_stride, G, nb * 16, Z + (int64_t)b0 * 16 * MS_D,
-                               z_stride);
-            ws += (int64_t)G * nb * 16 * MS_D;
+            hipLaunchKernelGGL(ms_hill_finish_kernel<L2>, dim3(Sc, M), dim3(1024), 0, st, ws, part_stride, G, nb * 16,
+                               Z + (int64_t)b0 * 16 * MS_D, z_stride);
+            ws += (int64_t)G * nb * 16 * PW;
         }
     }
     return MSM_OK;
@@ -1653,50 +1780,96 @@ extern "C" int msm_ms_select_seeds(const float* X, int M, int n, int d, int num_
     return MSM_OK;
 }
 
+// The Euclidean metric: the one-launch-per-step kernel only (the persistent kernels stay cosine-only), so no index is ever -1.
+extern "C" int msm_ms_select_seeds_l2(const float* X, int M, int n, int d, int num_seeds, const int64_t* first_indices, int64_t first_index,
+                                      float* seeds_out, int64_t* indices_out, float* workspace, int64_t workspace_elems, void* stream) {
+    MSM_REQUIRE(X && seeds_out && indices_out && workspace, "msm_ms_select_seeds_l2: null pointer");
+    MSM_REQUIRE(d == MS_D, "msm_ms_select_seeds_l2: d=%d, only d=64 is supported", d);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && num_seeds > 0, "msm_ms_select_seeds_l2: bad sizes (1 <= M <= %d)", MSB_MAXM);
+    MSM_REQUIRE(first_indices || (M == 1 && first_index >= 0 && first_index < n),
+                "msm_ms_select_seeds_l2: first_indices [M] on the device or, for one map, first_index in [0, n)");
+    MSM_REQUIRE(num_seeds <= MS_SB * 16, "msm_ms_select_seeds_l2: at most %d seeds", MS_SB * 16);
+    MSM_REQUIRE((((uintptr_t)X) & 15) == 0 && (((uintptr_t)workspace) & 7) == 0, "msm_ms_select_seeds_l2: misaligned pointer");
+    if (workspace_elems < msm_ms_seed_workspace(M, n)) {
+        set_error("msm_ms_select_seeds_l2: workspace too small");
+        return MSM_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const SeedWorkspace w = seed_workspace(workspace, M);
+    hipLaunchKernelGGL(ms_seed_init_kernel, dim3(cdiv(num_seeds, 64), M), dim3(64), 0, st, w.keys, MSB_KEYS, num_seeds, first_indices, first_index,
+                       n);
+    const int nblk = seed_blocks(n);
+    for (int i = 1; i < num_seeds; ++i)
+        if (n >= 16) hipLaunchKernelGGL((ms_seed_step_kernel<false, true>), dim3(nblk, M), dim3(256), 0, st, X, n, w.keys, MSB_KEYS, i, w.nearest);
+        else hipLaunchKernelGGL((ms_seed_step_kernel<true, true>), dim3(nblk, M), dim3(256), 0, st, X, n, w.keys, MSB_KEYS, i, w.nearest);
+    hipLaunchKernelGGL(ms_seed_finish_kernel, dim3(num_seeds, M), dim3(64), 0, st, X, w.keys, MSB_KEYS, indices_out, seeds_out,
+                       (const unsigned int*)nullptr, n);
+    MSM_CHECK_LAUNCH("msm_ms_select_seeds_l2");
+    return MSM_OK;
+}
+
 // partial sums of ONE map's workgroups
 extern "C" int64_t msm_ms_hill_climb_workspace(int n, int S) {
     const int nsb = cdiv(S, 16);
     return (int64_t)hill_wgs(n) * nsb * 16 * MS_D;
 }
 
-template <int NSB>
+template <int NSB, bool L2 = false>
 static int hill_chunk_launch(const float* X, int M, int n, const float* Zc, int64_t z_stride, int Sc, float kappa, float* ws,
                              int64_t part_stride, int G, hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)NSB * 16 * SZ + 4 * 16 * SZ);
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_hill_kernel<NSB>, lds));
-    hipLaunchKernelGGL((ms_hill_kernel<NSB>), dim3(G, M), dim3(256), lds, st, X, n, Zc, z_stride, Sc, kappa, ws, part_stride);
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_hill_kernel<NSB, L2>, lds));
+    hipLaunchKernelGGL((ms_hill_kernel<NSB, L2>), dim3(G, M), dim3(256), lds, st, X, n, Zc, z_stride, Sc, kappa, ws, part_stride);
+    return MSM_OK;
+}
+
+// the partial sums of the Euclidean form carry the sum of the weights: 65 floats per seed row
+extern "C" int64_t msm_ms_hill_climb_l2_workspace(int n, int S) {
+    const int nsb = cdiv(S, 16);
+    return (int64_t)hill_wgs(n) * nsb * 16 * (MS_D + 1);
+}
+
+template <bool L2>
+static int hill_climb_impl(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
+                           int64_t workspace_elems, void* stream) {
+    MSM_REQUIRE(X && Z && workspace, "msm_ms_hill_climb%s: null pointer", L2 ? "_l2" : "");
+    MSM_REQUIRE(d == MS_D, "msm_ms_hill_climb%s: d=%d, only d=64 is supported", L2 ? "_l2" : "", d);
+    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0,
+                "msm_ms_hill_climb%s: bad sizes (S <= %d, M <= %d)", L2 ? "_l2" : "", MS_SB * 16, MSB_MAXM);
+    MSM_REQUIRE((((uintptr_t)X) & 15) == 0, "msm_ms_hill_climb%s: X must be 16-byte aligned", L2 ? "_l2" : "");
+    const int64_t z_stride = (int64_t)S * MS_D, part_stride = L2 ? msm_ms_hill_climb_l2_workspace(n, S) : msm_ms_hill_climb_workspace(n, S);
+    if (workspace_elems < M * part_stride) {
+        set_error("msm_ms_hill_climb%s: workspace too small", L2 ? "_l2" : "");
+        return MSM_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int G = hill_wgs(n);
+    const int rc = hill_iterations<L2>(Z, M, z_stride, S, iters, workspace, part_stride, G, st, [&](const float* Zc, int Sc, int nb, float* ws) {
+        switch (nb) {
+            case 1: return hill_chunk_launch<1, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 2: return hill_chunk_launch<2, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 3: return hill_chunk_launch<3, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 4: return hill_chunk_launch<4, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 5: return hill_chunk_launch<5, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 6: return hill_chunk_launch<6, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            case 7: return hill_chunk_launch<7, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+            default: return hill_chunk_launch<8, L2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
+        }
+    });
+    if (rc != MSM_OK) return rc;
+    MSM_CHECK_LAUNCH(L2 ? "msm_ms_hill_climb_l2" : "msm_ms_hill_climb");
     return MSM_OK;
 }
 
 extern "C" int msm_ms_hill_climb(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
                                  int64_t workspace_elems, void* stream) {
-    MSM_REQUIRE(X && Z && workspace, "msm_ms_hill_climb: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_hill_climb: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && iters >= 0,
-                "msm_ms_hill_climb: bad sizes (S <= %d, M <= %d)", MS_SB * 16, MSB_MAXM);
-    MSM_REQUIRE((((uintptr_t)X) & 15) == 0, "msm_ms_hill_climb: X must be 16-byte aligned");
-    const int64_t z_stride = (int64_t)S * MS_D, part_stride = msm_ms_hill_climb_workspace(n, S);
-    if (workspace_elems < M * part_stride) {
-        set_error("msm_ms_hill_climb: workspace too small");
-        return MSM_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = hill_wgs(n);
-    const int rc = hill_iterations(Z, M, z_stride, S, iters, workspace, part_stride, G, st, [&](const float* Zc, int Sc, int nb, float* ws) {
-        switch (nb) {
-            case 1: return hill_chunk_launch<1>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 2: return hill_chunk_launch<2>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 3: return hill_chunk_launch<3>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 4: return hill_chunk_launch<4>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 5: return hill_chunk_launch<5>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 6: return hill_chunk_launch<6>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            case 7: return hill_chunk_launch<7>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-            default: return hill_chunk_launch<8>(X, M, n, Zc, z_stride, Sc, kappa, ws, part_stride, G, st);
-        }
-    });
-    if (rc != MSM_OK) return rc;
-    MSM_CHECK_LAUNCH("msm_ms_hill_climb");
-    return MSM_OK;
+    return hill_climb_impl<false>(X, M, n, d, Z, S, kappa, iters, workspace, workspace_elems, stream);
+}
+
+// iters x { W = exp(-kappa ||z - x||^2), Z = (W X) / clamp(sum_x W, min = 1) }
+extern "C" int msm_ms_hill_climb_l2(const float* X, int M, int n, int d, float* Z, int S, float kappa, int iters, float* workspace,
+                                    int64_t workspace_elems, void* stream) {
+    return hill_climb_impl<true>(X, M, n, d, Z, S, kappa, iters, workspace, workspace_elems, stream);
 }
 
 template <int NSBW>
@@ -1861,40 +2034,61 @@ extern "C" int msm_ms_hill_climb_bf16(const void* Xb, int n, int d, float* Z, in
             default: rc = hill_bf16_launch<10>((const uint16_t*)Xb, n, Z, S, nsb, kappa, workspace, G, st); break;
         }
         if (rc != MSM_OK) return rc;
-        hipLaunchKernelGGL(ms_hill_finish_kernel, dim3(S, 1), dim3(1024), 0, st, workspace, (int64_t)0, G, nsb * 16, Z, (int64_t)0);
+        hipLaunchKernelGGL(ms_hill_finish_kernel<false>, dim3(S, 1), dim3(1024), 0, st, workspace, (int64_t)0, G, nsb * 16, Z, (int64_t)0);
     }
     MSM_CHECK_LAUNCH("msm_ms_hill_climb_bf16");
     return MSM_OK;
 }
 
-extern "C" int msm_ms_assign(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
-                             int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
-    MSM_REQUIRE(X && Z && seed_labels && labels_out && counts, "msm_ms_assign: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_assign: d=%d, only d=64 is supported", d);
+template <bool L2>
+static int assign_impl(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels, int64_t* labels_out,
+                       int64_t* counts, int num_labels, void* stream) {
+    MSM_REQUIRE(X && Z && seed_labels && labels_out && counts, "msm_ms_assign%s: null pointer", L2 ? "_l2" : "");
+    MSM_REQUIRE(d == MS_D, "msm_ms_assign%s: d=%d, only d=64 is supported", L2 ? "_l2" : "", d);
     MSM_REQUIRE(M > 0 && M <= MSB_MAXM && n > 0 && S > 0 && S <= MS_SB * 16 && num_labels > 0 && num_labels <= 4096,
-                "msm_ms_assign: bad sizes");
+                "msm_ms_assign%s: bad sizes", L2 ? "_l2" : "");
     hipStream_t st = (hipStream_t)stream;
     MSM_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)M * (size_t)num_labels, st));
     const int nchunks = cdiv(cdiv(S, 16), MS_CH);
     const int G = hill_wgs(n);
     const size_t lds = sizeof(float) * ((size_t)nchunks * MS_CH * 16 * SZ + 4 * 16 * SZ) + sizeof(unsigned int) * (size_t)num_labels;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_kernel, lds));
-    hipLaunchKernelGGL(ms_assign_kernel, dim3(G, M), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_assign_kernel<L2>, lds));
+    hipLaunchKernelGGL(ms_assign_kernel<L2>, dim3(G, M), dim3(256), lds, st, X, n, Z, S, nchunks, seed_labels, labels_out,
                        reinterpret_cast<unsigned long long*>(counts), num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_assign");
+    MSM_CHECK_LAUNCH(L2 ? "msm_ms_assign_l2" : "msm_ms_assign");
+    return MSM_OK;
+}
+
+extern "C" int msm_ms_assign(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
+                             int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
+    return assign_impl<false>(X, M, n, d, Z, S, seed_labels, labels_out, counts, num_labels, stream);
+}
+
+extern "C" int msm_ms_assign_l2(const float* X, int M, int n, int d, const float* Z, int S, const int64_t* seed_labels,
+                                int64_t* labels_out, int64_t* counts, int num_labels, void* stream) {
+    return assign_impl<true>(X, M, n, d, Z, S, seed_labels, labels_out, counts, num_labels, stream);
+}
+
+template <bool L2>
+static int components_impl(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels, int32_t* num_labels, void* stream) {
+    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components%s: null pointer", L2 ? "_l2" : "");
+    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components%s: d=%d, only d=64 is supported", L2 ? "_l2" : "", d);
+    MSM_REQUIRE(M > 0 && S > 0 && S <= CC_MAXS, "msm_ms_connected_components%s: S=%d must be in 1..%d", L2 ? "_l2" : "", S, CC_MAXS);
+    const size_t lds = sizeof(float) * (size_t)S * (MS_D + 1) + sizeof(int) * 2 * (size_t)S;
+    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_kernel<L2>, lds));
+    hipLaunchKernelGGL(ms_components_kernel<L2>, dim3(M), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
+    MSM_CHECK_LAUNCH(L2 ? "msm_ms_connected_components_l2" : "msm_ms_connected_components");
     return MSM_OK;
 }
 
 extern "C" int msm_ms_connected_components(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
                                            int32_t* num_labels, void* stream) {
-    MSM_REQUIRE(Z && seed_labels && num_labels, "msm_ms_connected_components: null pointer");
-    MSM_REQUIRE(d == MS_D, "msm_ms_connected_components: d=%d, only d=64 is supported", d);
-    MSM_REQUIRE(M > 0 && S > 0 && S <= CC_MAXS, "msm_ms_connected_components: S=%d must be in 1..%d", S, CC_MAXS);
-    const size_t lds = sizeof(float) * (size_t)S * (MS_D + 1) + sizeof(int) * 2 * (size_t)S;
-    MSM_CHECK_HIP((hipError_t)ensure_dynamic_lds((const void*)ms_components_kernel, lds));
-    hipLaunchKernelGGL(ms_components_kernel, dim3(M), dim3(64), lds, (hipStream_t)stream, Z, S, epsilon, seed_labels, num_labels);
-    MSM_CHECK_LAUNCH("msm_ms_connected_components");
-    return MSM_OK;
+    return components_impl<false>(Z, M, S, d, epsilon, seed_labels, num_labels, stream);
+}
+
+extern "C" int msm_ms_connected_components_l2(const float* Z, int M, int S, int d, float epsilon, int64_t* seed_labels,
+                                              int32_t* num_labels, void* stream) {
+    return components_impl<true>(Z, M, S, d, epsilon, seed_labels, num_labels, stream);
 }
 
 extern "C" int msm_ms_relabel_largest_zero(int64_t* labels, int M, int n, const int64_t* counts, int num_labels,

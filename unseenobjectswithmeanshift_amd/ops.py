@@ -1135,21 +1135,37 @@ def _check_xb(xb, n, d, who):
     return xb
 
 
-def _ms_select_seeds(X, num_seeds, first, first_index, stepwise, give_up_mask):
+MS_METRICS = ("cosine", "euclidean")
+
+
+def _ms_l2(metric, who):
+    """True for the Euclidean entry points (msm_ms_*_l2), False for the cosine ones; anything else is not a metric."""
+    if metric not in MS_METRICS:
+        raise ValueError(f"{who}: metric must be 'cosine' or 'euclidean', not {metric!r}")
+    return metric == "euclidean"
+
+
+def _ms_select_seeds(X, num_seeds, first, first_index, stepwise, give_up_mask, metric="cosine"):
     """X (M,n,64); ``first`` int64 (M,) on the device, or None with the host scalar ``first_index`` (one map: nothing is copied)."""
     M, n, d = X.shape
     seeds = torch.empty((M, num_seeds, d), device=X.device, dtype=torch.float32)
     idx = torch.empty((M, num_seeds), device=X.device, dtype=torch.int64)
     need = lib().msm_ms_seed_workspace(M, n)
     ws = torch.empty((need,), device=X.device, dtype=torch.float32)
+    if _ms_l2(metric, "ms_select_seeds"):
+        # one launch per step whatever ``stepwise`` says: the persistent kernels, and with them the give-up, are cosine-only
+        rc = lib().msm_ms_select_seeds_l2(_p(X), M, n, d, num_seeds, _p(first), first_index, _p(seeds), _p(idx), _p(ws), need, _stream())
+        check(rc, "msm_ms_select_seeds_l2")
+        return seeds, idx
     rc = lib().msm_ms_select_seeds(_p(X), M, n, d, num_seeds, _p(first), first_index, _p(seeds), _p(idx), _p(ws), need,
                                    (1 if stepwise else 0) | (2 if give_up_mask else 0), give_up_mask, _stream())
     check(rc, "msm_ms_select_seeds")
     return seeds, idx
 
 
-def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=False, xb=None):
-    """Farthest-point seeding.  X (n,64) unit rows.  Returns (seeds (S,64), indices int64 (S,)).  The single-launch
+def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=False, xb=None, metric="cosine"):
+    """Farthest-point seeding.  X (n,64) unit rows (``metric`` "euclidean": any rows, distance ||x - s||_2, always one launch per
+    step and never a give-up; fp32 only, ``xb`` is not used).  Returns (seeds (S,64), indices int64 (S,)).  The single-launch
     persistent kernel (maps up to 393 216 rows) needs its workgroups co-resident; if other work holds the CUs it gives up
     and every index is -1 -- callers re-issue with ``stepwise=True`` (mean_shift.mean_shift_smart_init does).
     ``xb`` (ms_pack_bf16(X); precision "bf16"): maps beyond the fp32 persistent kernel's reach work on the bf16 copy -- one
@@ -1157,6 +1173,11 @@ def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=Fal
     launch per step over the copy; distances are those of the rounded points, so the indices may differ from the fp32 path's."""
     _c(X, "X")
     n, d = X.shape
+    if _ms_l2(metric, "ms_select_seeds"):
+        if xb is not None:
+            raise ValueError("ms_select_seeds: the bf16 copy (xb) serves the cosine metric only")
+        seeds, idx = _ms_select_seeds(X[None], num_seeds, None, int(first_index), True, 0, metric)
+        return seeds[0], idx[0]
     if xb is not None and n > 393216:
         _check_xb(xb, n, d, "ms_select_seeds")
         seeds = torch.empty((num_seeds, d), device=X.device, dtype=torch.float32)
@@ -1171,15 +1192,18 @@ def ms_select_seeds(X, num_seeds, first_index, stepwise=False, _test_give_up=Fal
     return seeds[0], idx[0]
 
 
-def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None):
-    """iters x { Z = normalize(exp(kappa Z X^T) X) }; returns the updated copy of Z.  precision "f32": fp32 MFMAs;
+def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None, metric="cosine"):
+    """iters x { Z = normalize(exp(kappa Z X^T) X) }; returns the updated copy of Z.  ``metric`` "euclidean": iters x
+    { W = exp(-kappa ||z - x||^2), Z = W X / clamp(sum W, min=1) }, precision "f32" only (anything else raises ValueError).  precision "f32": fp32 MFMAs;
     "f32_split": fp32 results from six bf16 MFMAs per product on exact three-term splits (msm_ms_hill_climb_split);
     "bf16": single bf16 products over the bf16 copy ``xb`` = ms_pack_bf16(X) (made here when not given), seeds as h + l terms."""
     if precision not in ("f32", "f32_split", "bf16"):
         raise ValueError(f"ms_hill_climb: precision must be 'f32', 'f32_split' or 'bf16', not {precision!r}")
+    if _ms_l2(metric, "ms_hill_climb") and precision != "f32":
+        raise ValueError(f"ms_hill_climb: the Euclidean metric has the exact fp32 plan only, not precision={precision!r}")
     _c(X, "X"), _c(Z, "Z")
     if precision == "f32":
-        return ms_hill_climb_batched(X[None], Z[None], kappa, iters)[0]
+        return ms_hill_climb_batched(X[None], Z[None], kappa, iters, metric)[0]
     n, d = X.shape
     S = Z.shape[0]
     Z = Z.clone()
@@ -1195,16 +1219,16 @@ def ms_hill_climb(X, Z, kappa, iters, precision="f32", xb=None):
     return Z
 
 
-def ms_assign(X, Z, seed_labels, num_labels):
-    """labels[i] = seed_labels[first argmin_s 0.5(1 - X_i.Z_s)], counts = bincount(labels)."""
-    labels, counts = ms_assign_batched(X[None], Z[None], seed_labels[None], num_labels)
+def ms_assign(X, Z, seed_labels, num_labels, metric="cosine"):
+    """labels[i] = seed_labels[first argmin_s 0.5(1 - X_i.Z_s)] (``metric`` "euclidean": argmin_s ||X_i - Z_s||), counts = bincount(labels)."""
+    labels, counts = ms_assign_batched(X[None], Z[None], seed_labels[None], num_labels, metric)
     return labels[0], counts[0]
 
 
-def ms_connected_components(Z, epsilon):
+def ms_connected_components(Z, epsilon, metric="cosine"):
     """mean_shift.py:41-76 on the device: Z (S,64) -> (seed_labels (S,) int64, num (2,) int32 = [labels that survive =
-    len(unique(seed_labels)), labels created])."""
-    seed_labels, num = ms_connected_components_batched(Z[None], epsilon)
+    len(unique(seed_labels)), labels created]).  ``metric`` "euclidean": membership ||z_j - z_i||_2 <= epsilon."""
+    seed_labels, num = ms_connected_components_batched(Z[None], epsilon, metric)
     return seed_labels[0], num[0]
 
 
@@ -1232,12 +1256,13 @@ def _first_indices_device(first_indices, M, n, device, who):
     return host.to(device)
 
 
-def ms_select_seeds_batched(X, num_seeds, first_indices, stepwise=False, _test_give_up=None):
+def ms_select_seeds_batched(X, num_seeds, first_indices, stepwise=False, _test_give_up=None, metric="cosine"):
     """ms_select_seeds for M maps of one size: X (M,n,64) unit rows, first_indices (M,) -> (seeds (M,S,64), indices int64 (M,S)),
     each map's bit-identical to ms_select_seeds(X[m], num_seeds, first_indices[m]).  Maps of 4096 .. 393 216 rows share grouped
     persistent launches (a map is held by cdiv(n, 1536) workgroups, as many maps per launch as the CUs hold); a group that loses
     co-residency reports -1 for its own map's indices only -- re-issue those maps with ``stepwise=True`` (one launch per step for
-    all maps; mean_shift.mean_shift_smart_init_batched does).  ``_test_give_up``: maps whose give-up flag starts raised (tests)."""
+    all maps; mean_shift.mean_shift_smart_init_batched does).  ``_test_give_up``: maps whose give-up flag starts raised (tests).
+    ``metric`` "euclidean": rows of any length, distance ||x - s||_2, one launch per step for every n -- no index is ever -1."""
     _c(X, "X")
     M, n, d = X.shape
     first = _first_indices_device(first_indices, M, n, X.device, "ms_select_seeds_batched")
@@ -1246,25 +1271,30 @@ def ms_select_seeds_batched(X, num_seeds, first_indices, stepwise=False, _test_g
         if not 0 <= int(m) < min(M, 64):
             raise RuntimeError("ms_select_seeds_batched: _test_give_up names maps 0 .. min(M, 64) - 1")
         mask |= 1 << int(m)
-    return _ms_select_seeds(X, num_seeds, first, 0, stepwise, mask)
+    return _ms_select_seeds(X, num_seeds, first, 0, stepwise, mask, metric)
 
 
-def ms_hill_climb_batched(X, Z, kappa, iters):
+def ms_hill_climb_batched(X, Z, kappa, iters, metric="cosine"):
     """ms_hill_climb (precision "f32") for M maps: X (M,n,64), Z (M,S,64) -> the updated copy of Z; a map's result does not depend
-    on its neighbours (same per-map grid, slab walk and summation order for every M)."""
+    on its neighbours (same per-map grid, slab walk and summation order for every M), with either ``metric``."""
     _c(X, "X"), _c(Z, "Z")
     M, n, d = X.shape
     if Z.dim() != 3 or Z.shape[0] != M or Z.shape[2] != d:
         raise RuntimeError(f"ms_hill_climb_batched: Z has shape {tuple(Z.shape)}, expected ({M}, S, {d})")
     S = Z.shape[1]
     Z = Z.clone()
+    if _ms_l2(metric, "ms_hill_climb_batched"):
+        need = M * lib().msm_ms_hill_climb_l2_workspace(n, S)
+        ws = torch.empty((need,), device=X.device, dtype=torch.float32)
+        check(lib().msm_ms_hill_climb_l2(_p(X), M, n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()), "msm_ms_hill_climb_l2")
+        return Z
     need = M * lib().msm_ms_hill_climb_workspace(n, S)
     ws = torch.empty((need,), device=X.device, dtype=torch.float32)
     check(lib().msm_ms_hill_climb(_p(X), M, n, d, _p(Z), S, float(kappa), int(iters), _p(ws), need, _stream()), "msm_ms_hill_climb")
     return Z
 
 
-def ms_assign_batched(X, Z, seed_labels, num_labels):
+def ms_assign_batched(X, Z, seed_labels, num_labels, metric="cosine"):
     """ms_assign for M maps: X (M,n,64), Z (M,S,64), seed_labels int64 (M,S) -> (labels int64 (M,n), counts int64 (M,num_labels))."""
     _c(X, "X"), _c(Z, "Z"), _c(seed_labels, "seed_labels", torch.int64)
     M, n, d = X.shape
@@ -1272,19 +1302,20 @@ def ms_assign_batched(X, Z, seed_labels, num_labels):
         raise RuntimeError(f"ms_assign_batched: Z {tuple(Z.shape)} / seed_labels {tuple(seed_labels.shape)} do not match X {tuple(X.shape)}")
     labels = torch.empty((M, n), device=X.device, dtype=torch.int64)
     counts = torch.empty((M, num_labels), device=X.device, dtype=torch.int64)
-    rc = lib().msm_ms_assign(_p(X), M, n, d, _p(Z), Z.shape[1], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
-    check(rc, "msm_ms_assign")
+    name = "msm_ms_assign_l2" if _ms_l2(metric, "ms_assign_batched") else "msm_ms_assign"
+    rc = getattr(lib(), name)(_p(X), M, n, d, _p(Z), Z.shape[1], _p(seed_labels), _p(labels), _p(counts), num_labels, _stream())
+    check(rc, name)
     return labels, counts
 
 
-def ms_connected_components_batched(Z, epsilon):
+def ms_connected_components_batched(Z, epsilon, metric="cosine"):
     """ms_connected_components for M seed sets, one wave each: Z (M,S,64) -> (seed_labels int64 (M,S), num int32 (M,2))."""
     _c(Z, "Z")
     M, S, d = Z.shape
     seed_labels = torch.empty((M, S), device=Z.device, dtype=torch.int64)
     num = torch.empty((M, 2), device=Z.device, dtype=torch.int32)
-    check(lib().msm_ms_connected_components(_p(Z), M, S, d, float(epsilon), _p(seed_labels), _p(num), _stream()),
-          "msm_ms_connected_components")
+    name = "msm_ms_connected_components_l2" if _ms_l2(metric, "ms_connected_components_batched") else "msm_ms_connected_components"
+    check(getattr(lib(), name)(_p(Z), M, S, d, float(epsilon), _p(seed_labels), _p(num), _stream()), name)
     return seed_labels, num
 
 

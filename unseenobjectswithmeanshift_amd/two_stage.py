@@ -34,6 +34,7 @@ the oracle.  Differences from the reference, on purpose:
     numbered in the order they were kept.
 """
 import collections
+import functools
 
 import numpy as np
 import torch
@@ -1110,14 +1111,17 @@ class BatchedTwoStage:
 # 224 x 224 crops -> clustering of every crop -> paste back.  The second stage clusters one small map per object; on the device
 # all of them go through ONE batched clustering (mean_shift.clustering_features -> mean_shift_smart_init_batched).
 # ----------------------------------------------------------------------------------------------------------------------
-def _cluster_fn(cluster, features):
+def _cluster_fn(cluster, features, metric="cosine"):
+    """A caller's ``cluster`` is used as it is; the default is mean_shift.clustering_features with ``metric`` bound."""
     if cluster is not None:
         return cluster
     if not features.is_cuda:
         raise RuntimeError("the clustering has no CPU path in unseenobjectswithmeanshift_amd: pass cluster= (e.g. the oracle's "
                            "clustering_features) for host tensors")
     from . import mean_shift
-    return mean_shift.clustering_features
+    if metric == "cosine":
+        return mean_shift.clustering_features
+    return functools.partial(mean_shift.clustering_features, metric=metric)
 
 
 def _take_first(first_indices, k, what):
@@ -1127,7 +1131,7 @@ def _take_first(first_indices, k, what):
 
 
 def test_sample_clustering(sample, network, network_crop=None, *, num_seeds=100, depth_threshold=0.8, first_indices=None, cluster=None,
-                           stages=None):
+                           stages=None, metric="cosine"):
     """lib/fcn/test_dataset.py:232-267, step for step -> (out_label (1,H,W), out_label_refined (1,H,W) or None).
     sample: {"image_color" (1,3,H,W), "depth" (1,3,H,W) xyz (optional: no depth, no depth filter), "label" (optional)};
     ``network(image, label, depth)`` returns unit-norm embeddings (1,C,H,W), ``network_crop(rgb_crop, mask_crop, depth_crop)``
@@ -1135,13 +1139,15 @@ def test_sample_clustering(sample, network, network_crop=None, *, num_seeds=100,
     in place of the reference's np.random.randint draws (MS:155), which are made here, in that order, when it is None.
     ``cluster``: the clustering_features to use -- default mean_shift.clustering_features on device tensors (the crops in one batched
     call); host tensors (the CPU tests of this logic) must pass one, e.g. the oracle's.  ``stages``: a dict that receives the
-    intermediate tensors (selected indices, ROIs, per-crop label images) -- for tests."""
+    intermediate tensors (selected indices, ROIs, per-crop label images) -- for tests.  ``metric``: "cosine" or "euclidean"
+    (cfg.TRAIN.EMBEDDING_METRIC; the networks then return un-normalised embeddings), forwarded to the default clustering; a
+    caller's ``cluster`` is called as before."""
     image = sample["image_color"]
     depth = sample.get("depth")
     label = sample.get("label")
     H, W = image.shape[-2:]
     features = network(image, label, depth).detach()                                             # TD:247
-    cluster = _cluster_fn(cluster, features)
+    cluster = _cluster_fn(cluster, features, metric)
     first = np.random.randint(0, H * W) if first_indices is None else _take_first(first_indices, 0, "the first stage")
     out_label, selected_pixels = cluster(features, num_seeds=num_seeds, first_indices=[first])   # TD:248
     raw_label = out_label
@@ -1166,7 +1172,7 @@ def test_sample_clustering(sample, network, network_crop=None, *, num_seeds=100,
 
 
 def test_batch_clustering(samples, network, network_crop=None, *, num_seeds=100, depth_threshold=0.8, first_indices=None, crop_batch=256,
-                          cluster=None, stages=None):
+                          cluster=None, stages=None, metric="cosine"):
     """test_sample_clustering for a list of F frames of one size -> (out_label (F,H,W), refined (F,H,W) or None, rows); frame f's
     results equal test_sample_clustering(samples[f], ...)[0][0] / [1][0] given the same first indices (the reference crops image 0
     of its batch only, so its batch is always 1: the semantics stay per frame).  ``rows`` is the ROI table (frame, label, x0, y0,
@@ -1175,7 +1181,8 @@ def test_batch_clustering(samples, network, network_crop=None, *, num_seeds=100,
     grouped seeding carries one map per launch); the second stage cuts every ROI of every frame in one launch, runs ``network_crop``
     on ``crop_batch`` crops at a time, clusters ALL N crops of the batch in one batched call and pastes every frame in one launch.
     ``first_indices``: per frame the sequence test_sample_clustering takes (first stage, then the frame's crops); None draws them
-    with np.random.randint -- the F first-stage indices, then the crops' in (frame, label) order."""
+    with np.random.randint -- the F first-stage indices, then the crops' in (frame, label) order.  ``metric`` as in
+    test_sample_clustering."""
     Fr = len(samples)
     images = torch.stack([s["image_color"][0] if s["image_color"].dim() == 4 else s["image_color"] for s in samples]).float().contiguous()
     with_depth = [s.get("depth") is not None for s in samples]
@@ -1189,7 +1196,7 @@ def test_batch_clustering(samples, network, network_crop=None, *, num_seeds=100,
         labels = torch.stack([torch.as_tensor(s["label"]).reshape(s["label"].shape[-2:]) for s in samples])
     _, _, H, W = images.shape
     features = network(images, labels, depths).detach()
-    cluster = _cluster_fn(cluster, features)
+    cluster = _cluster_fn(cluster, features, metric)
     if first_indices is not None and len(first_indices) != Fr:
         raise ValueError(f"first_indices must hold one sequence per frame ({Fr}), got {len(first_indices)}")
     firsts = [np.random.randint(0, H * W) if first_indices is None else _take_first(first_indices[f], 0, f"frame {f}'s first stage")
