@@ -68,7 +68,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 32   /* 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 33   /* 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1106,8 +1106,28 @@ int msm_eval_counts(const float* pred, const float* gt, int32_t* counts, void* w
  *                zero-initialised by the caller; only matched masks are written)
  *   flags        MSM_POINT_LOSS_GLOBAL_ATOMICS: scatter with global float atomics even where the mask fits in LDS
  *                (Hm Wm 4 <= 128 KiB: one workgroup accumulates its mask in LDS and writes it out whole).  The float atomics
- *                make the gradient's last bits depend on arrival order. */
+ *                make the gradient's last bits depend on arrival order.
+ *
+ * msm_lsap_match: the rectangular linear sum assignment of every (prediction, image) cost matrix of msm_match_cost, solved on
+ * the device by shortest augmenting paths (Crouse 2016, the algorithm of scipy's linear_sum_assignment) in float64 on the
+ * upcast costs, with the operation order and the tie rule of criterion.lsap_numpy (among equal minima the lowest free column,
+ * else the lowest column), so that the assignments equal lsap_numpy's bit for bit.  One workgroup of one wave per problem,
+ * counted loops only, no communication between workgroups.
+ *   cost         [n_pred][Q][TT] fp32 as msm_match_cost writes it
+ *   table        device int64 [2 (B + 1)]: toff[0..B], then poff[0..B] with poff[b] = sum_{b' < b} min(Q, T_b'), poff[B] = N
+ *   labels       [TT] int32
+ *   pairs        [n_pred N][4] int32 in msm_point_loss_fwd's layout (prediction, n, b Q + q, target row in tgt); problem
+ *                (p, b) writes rows p N + poff[b] .. p N + poff[b + 1], q ascending
+ *   target_classes [n_pred][B][Q] int64: labels[toff[b] + j] where query q is matched to target j, no_object elsewhere;
+ *                every element is written
+ *   status       [n_pred][B] int32: 0 solved; 1 the matrix holds nan or -inf; 2 infeasible (a row reaches no finite column);
+ *                3 a loop bound was hit (unreachable; a bug ends as a value, not as a hang).  A problem with a non-zero
+ *                status writes the fallback pairs (q = j, target j) for j < min(Q, T_b), so the consumer reads in bounds.
+ *   max_T        max_b (toff[b + 1] - toff[b]); max(Q, max_T) <= MSM_LSAP_MAX_DIM, else MSM_E_INVALID
+ *   The working matrix (transposed when T_b < Q: the solver iterates over the smaller side) is staged in LDS as fp32 and
+ *   upcast on use (exact) when Q max_T <= 28672 values, else read from `cost`. */
 #define MSM_POINT_LOSS_GLOBAL_ATOMICS 1
+#define MSM_LSAP_MAX_DIM 1024
 int msm_match_cost(const int64_t* table, const uint8_t* tgt, const int32_t* labels, const float* points, float* cost,
                    int n_pred, int B, int Q, int C1, int Hm, int Wm, int Hg, int Wg, int P, int TT, int max_T,
                    float w_class, float w_mask, float w_dice, void* stream);
@@ -1120,6 +1140,8 @@ int msm_point_loss_bwd(const int64_t* table, const uint8_t* tgt, const int32_t* 
                        const float* rnd_points, const void* workspace, int64_t workspace_bytes, const float* grad_losses,
                        int n_pred, int N, int BQ, int TT, int Hm, int Wm, int Hg, int Wg, int Pos, int k, int P,
                        float num_masks, int flags, void* stream);
+int msm_lsap_match(const float* cost, const int64_t* table, const int32_t* labels, int32_t* pairs, int64_t* target_classes,
+                   int32_t* status, int n_pred, int B, int Q, int TT, int max_T, int N, int no_object, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,11 +3,18 @@
 B = 8, Q = 100, 10 predictions of 120 x 160 masks, 8 targets of 480 x 640 per image, P = 12544 (oversample 3, importance 0.75).
 HIP events, median of --reps runs after --warmup.  --once: one forward + backward and nothing else (for
 `rocprofv3 --kernel-trace --stats -- python tools/probes/criterion_time.py --once`, which counts the launches of one call).
+
+--solver host|device|both (default both): the matcher's solver; every solver asked for is timed in the same process, forward
+and forward + backward, with the launch entry points' own times (kernel_ms, msm_lsap_match among them for "device").  Next to
+each event time stands `host_ms`: the wall time until the call RETURNS, i.e. how long the host is held before it can queue
+the next thing (the host solver waits for the GPU inside the call, the device solver does not).
+--targets T: targets per image (default 8); --targets 100 is the dense worst case of the assignment (100 x 100 per problem).
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -88,56 +95,73 @@ def torch_reference(outputs, targets, weights=(2.0, 5.0, 5.0), eos=0.1, oversamp
     return losses
 
 
-def timed(fn, reps, warmup):
+def timed(fn, reps, warmup, host=False):
+    """Median HIP-event time of fn(); host=True: (event time, wall time until fn returned)."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
-    ts = []
+    ts, hs = [], []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
+        t0 = time.perf_counter()
         fn()
+        hs.append((time.perf_counter() - t0) * 1e3)
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
-    return float(np.median(ts))
+    return (float(np.median(ts)), float(np.median(hs))) if host else float(np.median(ts))
 
 
 def main():
+    global T
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--solver", choices=("host", "device", "both"), default="both")
+    ap.add_argument("--targets", type=int, default=T, help="targets per image")
+    ap.add_argument("--no-torch-loop", action="store_true", help="skip the torch restatement of the reference's loop")
     a = ap.parse_args()
+    T = a.targets
     out, preds, targets = inputs()
-    crit = cr.build_criterion(C1 - 1, class_weight=2.0, mask_weight=5.0, dice_weight=5.0, no_object_weight=0.1, dec_layers=NP)
-
-    def ours_fwd():
-        return crit(out, targets)
-
-    def ours_step():
-        sum(ours_fwd().values()).backward()
+    solvers = ("host", "device") if a.solver == "both" else (a.solver,)
+    crits = {s: cr.build_criterion(C1 - 1, class_weight=2.0, mask_weight=5.0, dice_weight=5.0, no_object_weight=0.1, dec_layers=NP,
+                                   solver=s).to(DEV) for s in solvers}
 
     def ref_step():
         sum(torch_reference(out, targets).values()).backward()
 
     if a.once:
-        ours_step()
+        sum(crits[solvers[0]](out, targets).values()).backward()
         torch.cuda.synchronize()
         return
-    res = {"shape": dict(B=B, Q=Q, n_pred=NP, masks=[HM, WM], targets_per_image=T, target_size=[HG, WG], P=P)}
-    with torch.no_grad():
-        res["ours_forward_ms"] = timed(ours_fwd, a.reps, a.warmup)
-    res["ours_forward_backward_ms"] = timed(ours_step, a.reps, a.warmup)
-    with torch.no_grad():
-        res["torch_loop_forward_ms"] = timed(lambda: torch_reference(out, targets), a.reps, a.warmup)
-    res["torch_loop_forward_backward_ms"] = timed(ref_step, a.reps, a.warmup)
     from unseenobjectswithmeanshift_amd import _lib
-    with _lib.CallTimer() as ct:
+    res = {"shape": dict(B=B, Q=Q, n_pred=NP, masks=[HM, WM], targets_per_image=T, target_size=[HG, WG], P=P)}
+    for s in solvers:
+        crit = crits[s]
+
+        def fwd():
+            return crit(out, targets)
+
+        def step():
+            sum(fwd().values()).backward()
+
+        r = {}
         with torch.no_grad():
-            ours_fwd()
-    torch.cuda.synchronize()
-    res["kernel_ms"] = {k: round(sum(v), 4) for k, v in ct.durations().items()}
+            r["forward_ms"], r["forward_host_ms"] = timed(fwd, a.reps, a.warmup, host=True)
+        r["forward_backward_ms"], r["forward_backward_host_ms"] = timed(step, a.reps, a.warmup, host=True)
+        with _lib.CallTimer() as ct:
+            with torch.no_grad():
+                fwd()
+        torch.cuda.synchronize()
+        r["kernel_ms"] = {k: round(sum(v), 4) for k, v in ct.durations().items()}
+        crit.check_matching()
+        res[s] = r
+    if not a.no_torch_loop:
+        with torch.no_grad():
+            res["torch_loop_forward_ms"] = timed(lambda: torch_reference(out, targets), a.reps, a.warmup)
+        res["torch_loop_forward_backward_ms"] = timed(ref_step, a.reps, a.warmup)
     print(json.dumps(res))
 
 

@@ -24,6 +24,13 @@ the Philox offsets), and the same seed gives the reference's points.  A CPU ``ge
 Deviations: a batch without any target gives loss_mask = loss_dice = 0 with a zero gradient; all target masks of a batch must
 share one size (the reference pads them to the largest, which moves the normalised points of the smaller ones);
 ``num_points <= 0`` raises (the reference computes nan costs).
+
+``solver="device"`` (HungarianMatcher, build_criterion; the default is "host") replaces steps 3 and 4 by msm_lsap_match: the
+assignments are solved on the device exactly as ``lsap_numpy`` solves them (scipy's on every matrix whose optimum is
+unique), the kernel writes the pair table of step 5 and the target classes of step 6, and the call queues its launches
+without ever waiting for the GPU (targets on the device; ``average_num_masks`` of a distributed run aside).  What the host
+path raises at once, a nan / -inf or infeasible cost matrix, the device path records in ``last_status`` and reports only
+when ``check_matching()`` is called; the losses of such a call are those of the fallback assignment (q = j, target j).
 """
 import numpy as np
 import torch
@@ -107,6 +114,30 @@ def linear_sum_assignment(cost):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
+def indices_from_pairs(pairs_host, toff, Q, n_pred):
+    """The pair table of one criterion call on the host, (n_pred * N, 4) integer rows (prediction, n, b * Q + q, target row),
+    -> HungarianMatcher.solve's structure: per prediction, per image, the (i, j) int64 CPU tensors (queries, targets of the
+    image).  N = sum_b min(Q, T_b) with T_b = toff[b + 1] - toff[b]; image b's rows of a prediction are its next min(Q, T_b)."""
+    rows = torch.as_tensor(np.asarray(pairs_host), dtype=torch.int64).reshape(-1, 4)
+    counts = [min(int(Q), int(b) - int(a)) for a, b in zip(toff, toff[1:])]
+    N = sum(counts)
+    if rows.shape[0] != n_pred * N:
+        raise ValueError(f"indices_from_pairs: {rows.shape[0]} pairs, {n_pred} predictions x {N} expected")
+    out = []
+    for p in range(n_pred):
+        per, at = [], p * N
+        for b, n in enumerate(counts):
+            part = rows[at:at + n]
+            per.append(((part[:, 2] - b * int(Q)).clone(), (part[:, 3] - int(toff[b])).clone()))
+            at += n
+        out.append(per)
+    return out
+
+
+_STATUS_ERRORS = {1: (ValueError, "cost matrix contains nan or -inf"), 2: (ValueError, "cost matrix is infeasible"),
+                  3: (RuntimeError, "msm_lsap_match hit a loop bound (a bug in the solver)")}
+
+
 def average_num_masks(num_masks, device=None):
     """criterion.py:224-232: the number of target masks, all-reduced and divided by the world size when torch.distributed is
     initialised, clamped to at least 1, as a Python float (computed in float32 like the reference)."""
@@ -161,9 +192,12 @@ def _preds(outputs):
 
 class HungarianMatcher(nn.Module):
     """matcher.py:67-188 on msm_match_cost: the costs of all images (and, inside SetCriterion, all predictions) in one launch,
-    one device-to-host copy, then the assignment per image."""
+    one device-to-host copy, then the assignment per image.  solver="device": the assignments by msm_lsap_match, no copy and
+    no wait; forward then returns the (i, j) pairs as device tensors (a bad cost matrix gives the fallback pairs, see
+    ops.lsap_match; `last_status` holds the statuses)."""
 
-    def __init__(self, cost_class: float = 1, cost_mask: float = 1, cost_dice: float = 1, num_points: int = 0, generator=None):
+    def __init__(self, cost_class: float = 1, cost_mask: float = 1, cost_dice: float = 1, num_points: int = 0, generator=None,
+                 solver: str = "host"):
         super().__init__()
         self.cost_class = cost_class
         self.cost_mask = cost_mask
@@ -171,6 +205,10 @@ class HungarianMatcher(nn.Module):
         assert cost_class != 0 or cost_mask != 0 or cost_dice != 0, "all costs cant be 0"
         self.num_points = num_points
         self.generator = generator
+        if solver not in ("host", "device"):
+            raise ValueError(f"HungarianMatcher: solver must be 'host' or 'device', got {solver!r}")
+        self.solver = solver
+        self.last_status = None
 
     def _check(self):
         if int(self.num_points) <= 0:
@@ -208,15 +246,29 @@ class HungarianMatcher(nn.Module):
         torch.cuda.current_stream(cost.device).synchronize()
         return host
 
+    @staticmethod
+    def solve_device(cost, batch, no_object):
+        """cost (n_pred, Q, sum T) on the device -> ops.lsap_match's (pairs, target_classes, status); nothing waits."""
+        return ops.lsap_match(cost, batch.toff, batch.labels32, no_object)
+
     @torch.no_grad()
     def memory_efficient_forward(self, outputs, targets):
         self._check()
         dev = outputs["pred_masks"].device
-        B = outputs["pred_logits"].shape[0]
+        B, Q = outputs["pred_logits"].shape[:2]
         batch = _Batch(targets, dev)
         pts = torch.empty((1, B, int(self.num_points), 2), device=dev, dtype=torch.float32)
         self.draw_points(pts[0])
-        return self.solve(self.fetch(self.costs([outputs], batch, pts)), batch.toff)[0]
+        cost = self.costs([outputs], batch, pts)
+        if self.solver == "host":
+            return self.solve(self.fetch(cost), batch.toff)[0]
+        pairs, _, self.last_status = self.solve_device(cost, batch, 0)
+        out, at = [], 0
+        for b, t in enumerate(batch.T):                 # host-known counts: slices, no sync
+            part = pairs[at:at + min(Q, t)].to(torch.int64)
+            out.append((part[:, 2] - b * Q, part[:, 3] - batch.toff[b]))
+            at += min(Q, t)
+        return out
 
     @torch.no_grad()
     def forward(self, outputs, targets):
@@ -256,7 +308,12 @@ class SetCriterion(nn.Module):
 
     After a call, ``last_indices`` holds the assignments per prediction, ``last_points`` the draws (draw_points) and
     ``last_selection`` the importance-sampling selection bitmaps (n_pred * N, ceil(Pos / 32)) int32 (bit i % 32 of word
-    i / 32: oversampled point i)."""
+    i / 32: oversampled point i).
+
+    With a ``solver="device"`` matcher the call waits for nothing: ``last_indices`` is then built on first access (one copy
+    of the pair table and one sync, then the same lists of CPU tensor pairs), ``last_status`` is the device tensor
+    (n_pred, B) of msm_lsap_match's statuses, and a bad cost matrix is reported only by ``check_matching()``; until then the
+    losses of that call are those of the fallback assignment."""
 
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio, importance_sample_ratio,
                  generator=None):
@@ -276,6 +333,31 @@ class SetCriterion(nn.Module):
         self.last_indices = None
         self.last_points = None
         self.last_selection = None
+        self.last_status = None
+
+    @property
+    def last_indices(self):
+        if self._last_indices is None and self._last_pairs is not None:
+            pairs, toff, Q, n_pred = self._last_pairs
+            self._last_indices = indices_from_pairs(pairs.cpu().numpy(), toff, Q, n_pred)      # the copy and its sync
+        return self._last_indices
+
+    @last_indices.setter
+    def last_indices(self, value):
+        self._last_indices, self._last_pairs = value, None
+
+    def check_matching(self):
+        """Raise what the host solver would have raised during the last call: ValueError for a cost matrix with nan / -inf or
+        an infeasible one, RuntimeError if the device solver hit a loop bound.  Synchronises (it reads ``last_status``);
+        a no-op after a host-solver call, which raises at once."""
+        if self.last_status is None:
+            return
+        st = self.last_status.cpu()
+        bad = st.nonzero()
+        if bad.shape[0]:
+            p, b = (int(v) for v in bad[0])
+            err, msg = _STATUS_ERRORS.get(int(st[p, b]), (RuntimeError, f"unknown status {int(st[p, b])}"))
+            raise err(f"{msg} (prediction {p}, image {b})")
 
     def point_counts(self):
         """(P, Pos, k): points per mask, oversampled points, importance-sampled points (point_features.py's arithmetic)."""
@@ -320,25 +402,34 @@ class SetCriterion(nn.Module):
         self.last_points = (mp, os_, rnd)
         with torch.no_grad():
             cost = self.matcher.costs(preds, batch, mp)
-        indices = self.matcher.solve(self.matcher.fetch(cost), batch.toff)
-        self.last_indices = indices
+        device_solver = getattr(self.matcher, "solver", "host") == "device"
+        if device_solver:
+            # pairs and target classes straight from msm_lsap_match: no copy, no wait, no Python lists
+            with torch.no_grad():
+                pairs_t, target_classes, self.last_status = self.matcher.solve_device(cost, batch, self.num_classes)
+            self.last_indices = None
+            self._last_pairs = (pairs_t, list(batch.toff), Q, n_pred)
+        else:
+            indices = self.matcher.solve(self.matcher.fetch(cost), batch.toff)
+            self.last_indices = indices
+            self.last_status = None
+            # the matched pairs (b, q, target row) of each prediction in the reference's order (images in order, q ascending)
+            per_pred = [[(b, i, batch.toff[b] + j) for b, (I, J) in enumerate(indices[p]) for i, j in zip(I.tolist(), J.tolist())]
+                        for p in range(n_pred)]
         num_masks = average_num_masks(sum(batch.T), dev)
-
-        # the matched pairs (b, q, target row) of each prediction in the reference's order (images in order, q ascending)
-        per_pred = [[(b, i, batch.toff[b] + j) for b, (I, J) in enumerate(indices[p]) for i, j in zip(I.tolist(), J.tolist())]
-                    for p in range(n_pred)]
 
         parts = [dict() for _ in range(n_pred)]
         if "labels" in self.losses:
-            flat, tgt = [], []
-            for p, rows in enumerate(per_pred):
-                flat += [(p * B + b) * Q + q for b, q, _ in rows]
-                tgt += [t for _, _, t in rows]
-            target_classes = torch.full((n_pred * B * Q,), self.num_classes, dtype=torch.int64, device=dev)
-            if flat:
-                fi = torch.tensor(flat, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-                tj = torch.tensor(tgt, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-                target_classes[fi] = batch.labels[tj]
+            if not device_solver:
+                flat, tgt = [], []
+                for p, rows in enumerate(per_pred):
+                    flat += [(p * B + b) * Q + q for b, q, _ in rows]
+                    tgt += [t for _, _, t in rows]
+                target_classes = torch.full((n_pred * B * Q,), self.num_classes, dtype=torch.int64, device=dev)
+                if flat:
+                    fi = torch.tensor(flat, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+                    tj = torch.tensor(tgt, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+                    target_classes[fi] = batch.labels[tj]
             logits = torch.stack([p["pred_logits"].float() for p in preds])                       # (n_pred, B, Q, C+1)
             C1 = logits.shape[-1]
             w = self.empty_weight.to(dev, non_blocking=True)
@@ -349,8 +440,9 @@ class SetCriterion(nn.Module):
                 parts[p]["loss_ce"] = v
         if "masks" in self.losses:
             P, Pos, k = self.point_counts()
-            pairs = [(p, n, b * Q + q, t) for p, rows in enumerate(per_pred) for n, (b, q, t) in enumerate(rows)]
-            pairs_t = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 4).pin_memory().to(dev, non_blocking=True)
+            if not device_solver:
+                pairs = [(p, n, b * Q + q, t) for p, rows in enumerate(per_pred) for n, (b, q, t) in enumerate(rows)]
+                pairs_t = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 4).pin_memory().to(dev, non_blocking=True)
             state = {"tgt": batch.masks, "pairs": pairs_t, "os": os_, "rnd": rnd, "k": k, "num_masks": num_masks}
             masks = [p["pred_masks"].float().contiguous() for p in preds]
             lm = _PointLosses.apply(state, *masks)
@@ -389,10 +481,11 @@ def build_weight_dict(class_weight, mask_weight, dice_weight, dec_layers, deep_s
 
 
 def build_criterion(num_classes, *, class_weight, mask_weight, dice_weight, no_object_weight, dec_layers, deep_supervision=True,
-                    train_num_points=12544, oversample_ratio=3.0, importance_sample_ratio=0.75, generator=None):
-    """SetCriterion as meanshiftformer_model.py:134-176 builds it from the config (MODEL.MASK_FORMER.*)."""
+                    train_num_points=12544, oversample_ratio=3.0, importance_sample_ratio=0.75, generator=None, solver="host"):
+    """SetCriterion as meanshiftformer_model.py:134-176 builds it from the config (MODEL.MASK_FORMER.*).  solver: "host" (the
+    assignments by scipy after one device-to-host copy) or "device" (msm_lsap_match, no wait; see SetCriterion)."""
     matcher = HungarianMatcher(cost_class=class_weight, cost_mask=mask_weight, cost_dice=dice_weight, num_points=train_num_points,
-                               generator=generator)
+                               generator=generator, solver=solver)
     return SetCriterion(num_classes, matcher=matcher,
                         weight_dict=build_weight_dict(class_weight, mask_weight, dice_weight, dec_layers, deep_supervision),
                         eos_coef=no_object_weight, losses=["labels", "masks"], num_points=train_num_points,

@@ -1485,6 +1485,55 @@ def match_cost(logits, masks, tgt_masks, labels, toff, points, w_class=1.0, w_ma
     return cost
 
 
+LSAP_MAX_DIM = 1024     # MSM_LSAP_MAX_DIM: rows / columns of one assignment problem of msm_lsap_match
+
+
+def lsap_match(cost, toff, labels, no_object, out=None):
+    """The assignments of every (prediction, image) cost matrix of match_cost, solved on the device (msm_lsap_match), exactly
+    as criterion.lsap_numpy solves them.  cost (n_pred,Q,T) fp32 as match_cost returns it, toff: B + 1 host ints, labels (T,)
+    int32, no_object: the class of an unmatched query -> (pairs (n_pred*N,4) int32 rows (prediction, n, b*Q+q, target row) as
+    point_loss_fwd reads them, N = sum_b min(Q, T_b), images in order and q ascending; target_classes (n_pred,B,Q) int64;
+    status (n_pred,B) int32: 0 solved, 1 nan / -inf in the matrix, 2 infeasible, 3 a loop bound was hit; a problem with a
+    non-zero status holds the pairs (q = j, target j)).  out: (pairs, target_classes, status) tensors to write into.
+    Nothing here waits for the GPU: the statuses are for the caller to read when it chooses to."""
+    if cost.dim() != 3:
+        raise RuntimeError(f"lsap_match: cost must be (n_pred, Q, T), got {tuple(cost.shape)}")
+    n_pred, Q, TT = cost.shape
+    toff = [int(v) for v in toff]
+    B = len(toff) - 1
+    if B < 0 or toff[0] != 0 or toff[-1] != TT or any(b < a for a, b in zip(toff, toff[1:])):
+        raise RuntimeError(f"lsap_match: toff {toff} does not partition {TT} targets")
+    counts = [b - a for a, b in zip(toff, toff[1:])]
+    max_T = max(counts + [0])
+    if max(Q, max_T) > LSAP_MAX_DIM:
+        raise ValueError(f"lsap_match: {Q} queries x {max_T} targets: one side exceeds the supported {LSAP_MAX_DIM}")
+    if n_pred < 1 or Q < 1:
+        raise RuntimeError(f"lsap_match: cost {tuple(cost.shape)} needs at least one prediction and one query")
+    _c(cost, "cost"), _c(labels, "labels", torch.int32)
+    dev = cost.device
+    if labels.shape != (TT,) or labels.device != dev:
+        raise RuntimeError(f"lsap_match: labels {tuple(labels.shape)} on {labels.device} must be ({TT},) on {dev}")
+    poff = [0]
+    for t in counts:
+        poff.append(poff[-1] + min(Q, t))
+    N = poff[-1]
+    if out is None:
+        pairs = torch.empty((n_pred * N, 4), device=dev, dtype=torch.int32)
+        target_classes = torch.empty((n_pred, B, Q), device=dev, dtype=torch.int64)
+        status = torch.empty((n_pred, B), device=dev, dtype=torch.int32)
+    else:
+        pairs, target_classes, status = out
+        _c(pairs, "pairs", torch.int32), _c(target_classes, "target_classes", torch.int64), _c(status, "status", torch.int32)
+        if (pairs.shape != (n_pred * N, 4) or target_classes.shape != (n_pred, B, Q) or status.shape != (n_pred, B)
+                or {pairs.device, target_classes.device, status.device} != {dev}):
+            raise RuntimeError(f"lsap_match: out must be ({n_pred * N}, 4) int32, ({n_pred}, {B}, {Q}) int64 and ({n_pred}, {B}) "
+                               f"int32 on {dev}")
+    table = _device_table(toff + poff, dev)
+    check(lib().msm_lsap_match(_p(cost), _p(table), _p(labels), _p(pairs), _p(target_classes), _p(status), n_pred, B, Q, TT,
+                               max_T, N, int(no_object), _stream()), "msm_lsap_match")
+    return pairs, target_classes, status
+
+
 def _point_loss_args(masks, tgt_masks, pairs, os_points, rnd_points, k):
     _check_preds(masks, "masks", 4)
     dev = masks[0].device
