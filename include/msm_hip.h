@@ -47,6 +47,7 @@
  *                                   MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:337-343,461-497
  *   msm_instance_postprocess_resized
  *                                <- the same with sem_seg_postprocess's resize to the requested output size in between, :351-357
+ *   msm_embloss_fwd / _bwd       <- EmbeddingLoss lib/networks/embedding.py:57-133 (= MSMFormer/meanshiftformer/embedding.py)
  *   msm_mask_nms                 <- nms lib/fcn/nms.py:3-23 + combine_masks_with_NMS lib/fcn/test_utils.py:55-91, batched
  *   msm_ingest_frames            <- read_sample tools/test_image_with_ms_transformer.py:115-147, run_network
  *                                   ros/test_images_segmentation_transformer.py:159-173, compute_xyz lib/fcn/get_backbone.py:96-102
@@ -68,7 +69,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 33   /* 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 34   /* 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1142,6 +1143,40 @@ int msm_point_loss_bwd(const int64_t* table, const uint8_t* tgt, const int32_t* 
                        float num_masks, int flags, void* stream);
 int msm_lsap_match(const float* cost, const int64_t* table, const int32_t* labels, int32_t* pairs, int64_t* target_classes,
                    int32_t* status, int n_pred, int B, int Q, int TT, int max_T, int N, int no_object, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * EmbeddingLoss (lib/networks/embedding.py:57-133): the clustering loss of the UCN embedding network and the extra term of the
+ * MSMFormer RGB-D fine-tuning, forward and backward on per-(image, cluster) sums instead of the reference's four loops over the
+ * clusters with (B,C,H,W) temporaries.  No host synchronisation: K is found on the device.
+ *   x        [B][C][HW] fp32 (NCHW), labels [B][HW] fp32: pixel p belongs to cluster k iff label == k exactly, is "labelled"
+ *            iff label >= 0; a labelled pixel of no cluster (a non-integer label, or an integer >= max_clusters) is a "stray"
+ *            with centre 0, as a pixel no mask selects is in the reference.  K = int(max label) + 1 over the batch (1 when no
+ *            pixel is labelled; the reference divides by zero there).
+ *   per (b, k): n pixels, S = sum x_p, m = S / (n + 1e-10), mu = m / max(|m|, 1e-12) when normalize, else m (an empty cluster
+ *            has mu = 0 and still takes part in the inter term and in K)
+ *   d_p      metric 0 (cosine): labelled (1 - x_p . mu_k(p)) / 2; metric 1 (euclidean): labelled |x_p - mu_k(p)|
+ *   N_bk = #{p in k : d_p > alpha}, D_bk = sum_{p in k} d_p^2
+ *   intra    = lambda_intra / B [ sum_bk D_bk / (K max(N_bk, 50)) + sum_strays d_p^2 / (50 K) ] when any labelled pixel has
+ *            d_p > alpha (torch.sum(intra_cluster_mask) > 0, strays included), else 0
+ *   inter    = lambda_inter sum_b sum_{i != j} max(delta - dist(mu_i, mu_j), 0)^2 / (K (K - 1) / 2 B) for K > 1, else 0
+ *   losses   [3] fp32: intra + inter, intra, inter
+ *   info     [4 + 2 B max_clusters] int32: K, status (bit 0: a label >= max_clusters was met and treated as a stray), the
+ *            branch flag of intra, 0; then n [B][max_clusters], N [B][max_clusters] (zero from K on)
+ *   workspace msm_embloss_workspace(B, C, HW, max_clusters) bytes (device, 4-byte aligned); the forward leaves the centres,
+ *            the per-cluster coefficients and the centre-path vectors there for msm_embloss_bwd
+ * msm_embloss_bwd: grad_losses [3] (device) = d/d (loss, intra, inter) in any combination -> grad_x [B][C][HW], every element
+ * written: the direct part through d_p plus a C-vector per (b, k) (the gradient with respect to the centre, taken back through
+ * the normalisation, times 1 / (n + 1e-10)); N_bk and the zero branch carry no gradient, nothing enters an empty cluster, the
+ * Euclidean d^2 is differentiated as |x - mu|^2 (smooth at 0).
+ * Deterministic: pixel ranges per workgroup depend on the shape alone, partial sums are added in a fixed order, no
+ * floating-point atomics.  0 < B <= 65535, C >= 1, HW >= 1, 1 <= max_clusters <= 1024, max_clusters C <= 16384 (the per-wave
+ * table in LDS), else MSM_E_INVALID (the workspace query too); a workspace that is too small returns MSM_E_WORKSPACE. */
+int64_t msm_embloss_workspace(int B, int C, int HW, int max_clusters);
+int msm_embloss_fwd(const float* x, const float* labels, float* losses, int32_t* info, void* workspace, int64_t workspace_bytes,
+                    int B, int C, int HW, int max_clusters, int metric, int normalize, float alpha, float delta,
+                    float lambda_intra, float lambda_inter, void* stream);
+int msm_embloss_bwd(const float* x, const float* labels, const float* grad_losses, const void* workspace,
+                    int64_t workspace_bytes, float* grad_x, int B, int C, int HW, int max_clusters, int metric, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1643,6 +1643,90 @@ def mask_nms(masks, scores, candidate, thresh=0.7, workspace=None):
     return label, score_img, bbox, count, inst_labels
 
 
+EMBLOSS_METRICS = {"cosine": 0, "euclidean": 1}
+EMBLOSS_TABLE_FLOATS = 16384     # max_clusters * C: the per-wave table of msm_embloss_fwd in LDS (64 KiB)
+EMBLOSS_MAX_CLUSTERS = 1024
+
+
+def embloss_max_clusters(C, max_clusters=None):
+    """The cluster-table rows of msm_embloss_fwd for C channels: min(64, 16384 // C) by default; a request the table cannot hold
+    raises ValueError (before any launch)."""
+    C = int(C)
+    if C < 1:
+        raise ValueError(f"EmbeddingLoss: C must be at least 1, got {C}")
+    if max_clusters is None:
+        max_clusters = min(64, EMBLOSS_TABLE_FLOATS // C)
+    max_clusters = int(max_clusters)
+    if max_clusters < 1 or max_clusters > EMBLOSS_MAX_CLUSTERS or max_clusters * C > EMBLOSS_TABLE_FLOATS:
+        raise ValueError(f"EmbeddingLoss: max_clusters = {max_clusters} with C = {C} is outside 1 <= max_clusters <= "
+                         f"{EMBLOSS_MAX_CLUSTERS}, max_clusters * C <= {EMBLOSS_TABLE_FLOATS} (the cluster table lives in LDS)")
+    return max_clusters
+
+
+def embloss_workspace_bytes(B, C, HW, max_clusters):
+    """Bytes of workspace msm_embloss_fwd / _bwd need (partial tables, centres, centre-path vectors)."""
+    n = lib().msm_embloss_workspace(int(B), int(C), int(HW), int(max_clusters))
+    if n < 0:
+        check(int(n), "msm_embloss_workspace")
+    return int(n)
+
+
+def _embloss_args(x, labels, max_clusters, metric):
+    if metric not in EMBLOSS_METRICS:
+        raise ValueError(f"EmbeddingLoss: metric must be 'cosine' or 'euclidean', got {metric!r}")
+    if x.dim() != 4:
+        raise RuntimeError(f"x must be (B,C,H,W), got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    Kt = embloss_max_clusters(C, max_clusters)          # the size limits raise first: they need no device
+    _chk(x, "x"), _chk(labels, "labels")
+    if B < 1 or H * W < 1 or labels.numel() != B * H * W:
+        raise RuntimeError(f"x (B,C,H,W) = {tuple(x.shape)} needs B, H W >= 1 and labels (B,1,H,W), got {tuple(labels.shape)}")
+    _c(x, "x"), _c(labels, "labels")
+    return B, C, H * W, Kt
+
+
+def embloss_fwd(x, labels, alpha, delta, lambda_intra, lambda_inter, metric="cosine", normalize=True, max_clusters=None,
+                workspace=None):
+    """msm_embloss_fwd (the definition is in include/msm_hip.h): x (B,C,H,W) float32, labels (B,1,H,W) or (B,H,W) float32, both
+    contiguous on the GPU -> (losses (3,) = loss, intra, inter; info int32; workspace), six launches, no host synchronisation.
+    ``info`` = [K, status, branch flag, 0, n (B,Kt), N (B,Kt)] (embloss_info splits it); the workspace holds what embloss_bwd
+    reads, so a caller that passes its own (a uint8 tensor of embloss_workspace_bytes(...) bytes, for a HIP graph) must run the
+    backward before the next forward on it."""
+    B, C, HW, Kt = _embloss_args(x, labels, max_clusters, metric)
+    need = embloss_workspace_bytes(B, C, HW, Kt)
+    if workspace is None:
+        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    _c(workspace, "workspace", torch.uint8)
+    losses = torch.empty(3, device=x.device, dtype=torch.float32)
+    info = torch.empty(4 + 2 * B * Kt, device=x.device, dtype=torch.int32)
+    rc = lib().msm_embloss_fwd(_p(x), _p(labels), _p(losses), _p(info), _p(workspace), workspace.numel(), B, C, HW, Kt,
+                               EMBLOSS_METRICS[metric], int(bool(normalize)), float(alpha), float(delta), float(lambda_intra),
+                               float(lambda_inter), _stream())
+    check(rc, "msm_embloss_fwd")
+    return losses, info, workspace
+
+
+def embloss_bwd(x, labels, grad_losses, workspace, metric="cosine", max_clusters=None):
+    """msm_embloss_bwd: grad_losses (3,) float32 on the GPU (d/d loss, intra, inter) and the workspace of the forward on the
+    same x and labels -> grad_x, one launch."""
+    B, C, HW, Kt = _embloss_args(x, labels, max_clusters, metric)
+    _c(grad_losses, "grad_losses"), _c(workspace, "workspace", torch.uint8)
+    if grad_losses.numel() != 3:
+        raise RuntimeError(f"grad_losses must hold 3 values, got {tuple(grad_losses.shape)}")
+    grad_x = torch.empty_like(x)
+    rc = lib().msm_embloss_bwd(_p(x), _p(labels), _p(grad_losses), _p(workspace), workspace.numel(), _p(grad_x), B, C, HW, Kt,
+                               EMBLOSS_METRICS[metric], _stream())
+    check(rc, "msm_embloss_bwd")
+    return grad_x
+
+
+def embloss_info(info, B):
+    """info of embloss_fwd -> dict(K, status, flag: 0-d int32 views; n, N: (B, max_clusters) int32 views).  Device tensors:
+    reading them synchronises (tests and EmbeddingLoss.check())."""
+    Kt = (info.numel() - 4) // (2 * B)
+    return dict(K=info[0], status=info[1], flag=info[2], n=info[4:4 + B * Kt].view(B, Kt), N=info[4 + B * Kt:].view(B, Kt))
+
+
 def crop_resize(rgb, depth, labels, table, size):
     """ROI crops of a batch of frames in one launch (msm_crop_resize): rgb / depth (F,3,H,W), labels (F,H,W) float, table (N,8)
     int32 rows (frame, label, x0, y0, x1, y1, 0, 0) -> (rgb_crops (N,3,S,S), mask_crops (N,S,S), depth_crops or None)."""
