@@ -292,6 +292,56 @@ def conv3x3_tokens_to_nchw(t, w_tap_major, bias, H, W, bf16=False):
     return out
 
 
+def conv3x3_weight_grad(tok, gout, H, W, *, splits=None, want_bias=True):
+    """Weight and bias gradient of the 3x3 / pad 1 convolution of a 64-channel token map (the backward of conv3x3_tokens_to_nchw
+    with respect to its weight and bias; csrc/conv3x3_bwd.hip): tok (B, H*W, 64) the forward's input, gout (B, Cout, H, W) or
+    (B, Cout, H*W) the gradient of its NCHW output, Cout a multiple of 64 up to 1024, any H, W.  Returns (dw (Cout, 576) tap-major,
+    dbias (Cout,) or None when not ``want_bias``).  ``splits``: the number of pixel ranges whose partial sums are added in a
+    second launch (None: chosen by shape); the result is bit-identical from call to call for a given (shape, splits)."""
+    _c(tok, "tok"), _c(gout, "gout")
+    if tok.dim() != 3 or gout.dim() not in (3, 4):
+        raise RuntimeError("conv3x3_weight_grad needs tok (B, H*W, 64) and gout (B, Cout, H, W)")
+    B, HW, C = tok.shape
+    Cout = gout.shape[1]
+    if C != 64 or HW != H * W or gout.shape[0] != B or gout.numel() != B * Cout * HW:
+        raise RuntimeError("conv3x3_weight_grad needs tok (B, H*W, 64) and gout (B, Cout, H, W)")
+    splits = 0 if splits is None else int(splits)
+    if splits < 0:
+        raise RuntimeError("conv3x3_weight_grad: splits must be None or >= 1")
+    n = lib().msm_conv3x3_c64_wgrad_workspace(B, H, W, Cout, splits)
+    if n < 0:
+        check(int(n), "msm_conv3x3_c64_wgrad_workspace")
+    ws = torch.empty((n,), device=tok.device, dtype=torch.float32)
+    dw = torch.empty((Cout, 9 * C), device=tok.device, dtype=torch.float32)
+    db = torch.empty((Cout,), device=tok.device, dtype=torch.float32) if want_bias else None
+    rc = lib().msm_conv3x3_c64_wgrad(_p(tok), _p(gout), _p(dw), _p(db), _p(ws), B, H, W, Cout, splits, _stream())
+    check(rc, "msm_conv3x3_c64_wgrad")
+    return dw, db
+
+
+def conv3x3_input_grad(gout, w, H, W):
+    """Input gradient of the 3x3 / pad 1 convolution y = conv2d(x, w, padding=1): gout (B, Cout, H, W) the gradient of y, w the
+    parameter (Cout, Cin, 3, 3) -> (B, Cin, H, W).  It is the convolution of gout with the mirrored taps,
+    w'[c][(dy*3 + dx)*Cout + o] = w[o][c][2 - dy][2 - dx]: gout transposed once to tokens (msm_transpose_f32), the weight rearranged on
+    the device, then the implicit-GEMM mode of msm_gemm_f32 writing NCHW planes."""
+    _c(gout, "gout"), _chk(w, "w")
+    if gout.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != gout.shape[1] or tuple(gout.shape[2:]) != (H, W):
+        raise RuntimeError("conv3x3_input_grad needs gout (B, Cout, H, W) and w (Cout, Cin, 3, 3)")
+    B, Cout = gout.shape[:2]
+    Cin = w.shape[1]
+    HW = H * W
+    if Cout % 4:
+        raise RuntimeError("conv3x3_input_grad needs Cout a multiple of 4")
+    gtok = transpose_last2(gout.view(B, Cout, HW))                                          # (B, HW, Cout)
+    wm = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cin, 9 * Cout).contiguous()
+    out = torch.empty((B, Cin, HW), device=gout.device, dtype=torch.float32)
+    rc = lib().msm_gemm_f32(_p(gtok), None, _p(wm), None, _p(out), HW, Cin, 9 * Cout, B,
+                            Cout, 1, HW * Cout, 0, 0, 1, HW, Cin * HW, 0,
+                            2, H, W, Cout, 0, 0, 1, _stream())
+    check(rc, "msm_gemm_f32(conv3x3 input gradient)")
+    return out.view(B, Cin, H, W)
+
+
 def layernorm(x, g1, b1, *, parts=None, bias=None, l2norm=False, g2=None, b2=None, eps=1e-5):
     """LayerNorm(x + sum(parts) + bias) [-> unit length] [-> second LayerNorm].  Returns y or (y, y2)."""
     _c(x, "x"), _c(parts, "parts"), _c(bias, "bias"), _c(g1, "g1"), _c(b1, "b1"), _c(g2, "g2"), _c(b2, "b2")

@@ -10,6 +10,10 @@ are torch.autograd.Function wrappers whose forward AND backward run in libmsm_hi
     Q x pixel-embedding mask step   forward msm_mask_logits_fwd (logits + the NON-differentiable attention-mask bits of the
                                     next layer, detached in the reference too, DEC:680); backward two GEMMs per image
     MSDeformAttn core (pixel decoder)  MultiScaleDeformableAttention.ms_deform_attn_forward / _backward (round 1)
+    3x3 mask_features convolution   forward msm_conv3x3_c64_nchw_f32 (implicit GEMM when W % 4 != 0); backward
+                                    msm_conv3x3_c64_wgrad (weight, bias) and the implicit GEMM on the mirrored taps (input):
+                                    ``conv3x3``; with it ``head_forward_train`` / ``head_losses`` train the RGB-D head
+                                    (SimpleBasePixelDecoder + the single-level decoder) from the embedding to the loss dict
 
 and the cheap row-local glue (LayerNorm, ReLU, residual adds, L2 normalisation of 256-wide rows: < 1 % of the FLOPs) is left to
 torch's own differentiable elementwise ops on the device tensors.  ``decoder_forward_train`` follows the reference's literal
@@ -207,6 +211,70 @@ def decoder_forward_train(dec, x, mask_features):
             "aux_outputs": [{"pred_logits": a, "pred_masks": b} for a, b in zip(pred_cls[:-1], pred_mask[:-1])]}
 
 
+class _Conv3x3(torch.autograd.Function):
+    """y = conv2d(x, weight, bias, padding=1) for a 64-channel map (SimpleBasePixelDecoder.mask_features, fpn.py:237-246,281-284): the
+    forward is the inference path's (transpose to tokens, then the weight-stationary kernel when W % 4 == 0 and the implicit GEMM
+    otherwise); backward: msm_conv3x3_c64_wgrad on the saved token map for weight and bias, ops.conv3x3_input_grad (the mirrored
+    convolution of the gradient on the implicit GEMM) for the input.  fp32 only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        B, C, H, W = x.shape
+        Cout = weight.shape[0]
+        if C != 64 or tuple(weight.shape) != (Cout, 64, 3, 3) or Cout % 64 or Cout > 1024:
+            raise RuntimeError("training.conv3x3 needs x (B, 64, H, W) and weight (Cout, 64, 3, 3) with Cout a multiple of 64 up to 1024")
+        tok = ops.transpose_last2(x.contiguous().view(B, C, H * W))                       # NHWC tokens
+        w = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * C).contiguous()
+        y = ops.conv3x3_tokens_to_nchw(tok, w, None if bias is None else bias.contiguous(), int(H), int(W))
+        ctx.save_for_backward(tok, weight)
+        ctx.has_bias = bias is not None
+        ctx.hw = (int(H), int(W))
+        return y.view(B, Cout, H, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        tok, weight = ctx.saved_tensors
+        H, W = ctx.hw
+        g = g.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.conv3x3_input_grad(g, weight, H, W)
+        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_bias:
+            dw, gb = ops.conv3x3_weight_grad(tok, g, H, W, want_bias=want_bias)
+            if ctx.needs_input_grad[1]:
+                Cout = weight.shape[0]
+                gw = dw.view(Cout, 3, 3, 64).permute(0, 3, 1, 2).contiguous()              # tap-major -> (Cout, 64, 3, 3)
+        return gx, gw, gb
+
+
+def conv3x3(x, weight, bias=None):
+    """Differentiable 3x3 / pad 1 convolution of a (B, 64, H, W) map, both passes in libmsm_hip.so: weight (Cout, 64, 3, 3),
+    bias (Cout,) or None -> (B, Cout, H, W)."""
+    return _Conv3x3.apply(x, weight, bias)
+
+
+def head_forward_train(head, features):
+    """Differentiable MeanShiftMaskFormerHead.layers for the RGB-D configuration (pixel decoder SimpleBasePixelDecoder + the
+    single-level decoder; meanshift_former_head.py:121-126, fpn.py:274-290): ``features`` {"res5": (B, 64, H, W)} the channel-
+    normalised embedding; mask_features = conv3x3(embedding) (the embedding itself when mask_dim == 64, fpn.py:281-284), then
+    decoder_forward_train.  Returns {"pred_logits", "pred_masks", "aux_outputs"}; gradients reach the embedding, the convolution
+    and the decoder.  The head's inference ``forward`` is untouched."""
+    from .modeling import SimpleBasePixelDecoder
+    pd = head.pixel_decoder
+    if not isinstance(pd, SimpleBasePixelDecoder):
+        raise NotImplementedError(f"head_forward_train: {type(pd).__name__} (MSDeformAttnPixelDecoder) is not yet differentiable; "
+                                  "only SimpleBasePixelDecoder is")
+    if len(pd.in_features) != 1:
+        raise NotImplementedError("head_forward_train: the RGB-D pixel decoder takes one feature map (the embedding)")
+    y = features[pd.in_features[0]]
+    if pd.mask_dim == 64:
+        mask_features = y
+    else:
+        mask_features = conv3x3(y, pd.mask_features.weight, pd.mask_features.bias)
+    return decoder_forward_train(head.predictor, [y], mask_features)
+
+
 def weighted_losses(losses, weight_dict):
     """meanshiftformer_model.py:279-285: every loss with a weight in ``weight_dict`` times that weight; the others dropped."""
     return {k: v * weight_dict[k] for k, v in losses.items() if k in weight_dict}
@@ -216,3 +284,21 @@ def decoder_losses(dec, x, mask_features, targets, criterion):
     """decoder_forward_train -> criterion (criterion.SetCriterion) -> weighted_losses: the weighted loss dict of one training
     step of the decoder; ``sum(decoder_losses(...).values()).backward()`` runs every backward on the HIP kernels."""
     return weighted_losses(criterion(decoder_forward_train(dec, x, mask_features), targets), criterion.weight_dict)
+
+
+def head_losses(head, embedding, targets, criterion, *, labels=None, embedding_loss=None, embedding_weight=None):
+    """The training branch of the RGB-D meta-arch (pretrained_meanshiftformer_model.py:298-333) from the backbone's embedding
+    (B, 64, H, W) to the weighted loss dict: F.normalize over channels (once), head_forward_train, ``criterion``, and -- with
+    ``embedding_loss`` (embedding_loss.EmbeddingLoss; ``labels`` and ``embedding_weight`` are then required) --
+    losses["embedding_loss"] = embedding_loss(normalised, labels)[0] times that weight.  ``criterion.weight_dict`` is left as it is
+    (the reference writes the embedding weight into it, :323)."""
+    if embedding_loss is not None and (labels is None or embedding_weight is None):
+        raise ValueError("head_losses: embedding_loss needs labels and embedding_weight")
+    norm = F.normalize(embedding, p=2, dim=1)
+    outputs = head_forward_train(head, {head.pixel_decoder.in_features[0]: norm})
+    losses = criterion(outputs, targets)
+    weights = dict(criterion.weight_dict)
+    if embedding_loss is not None:
+        losses["embedding_loss"] = embedding_loss(norm, labels)[0]
+        weights["embedding_loss"] = embedding_weight
+    return weighted_losses(losses, weights)
