@@ -1134,6 +1134,7 @@ class MSDeformAttnPixelDecoder(PlanAttributes, nn.Module):
             d_model=conv_dim, dropout=transformer_dropout, nhead=transformer_nheads,
             dim_feedforward=transformer_dim_feedforward, num_encoder_layers=transformer_enc_layers,
             num_feature_levels=self.transformer_num_feature_levels)
+        self.transformer_dropout = float(transformer_dropout)    # inference ignores it; training.pixel_decoder_forward_train refuses > 0
         self.pe_layer = PositionEmbeddingSine(conv_dim // 2, normalize=True)
         self.mask_dim = mask_dim
         self.conv_dim = conv_dim

@@ -342,6 +342,88 @@ def conv3x3_input_grad(gout, w, H, W):
     return out.view(B, Cin, H, W)
 
 
+def conv3x3_input_grad_tokens(gtok, w, H, W):
+    """conv3x3_input_grad on token maps: gtok (B, H*W, Cout) the gradient of the token output of conv3x3_c64 / conv3x3_tokens, w the
+    parameter (Cout, Cin, 3, 3) -> (B, H*W, Cin).  The same implicit GEMM on the mirrored taps, reading and writing tokens: no
+    transposes."""
+    _c(gtok, "gtok"), _chk(w, "w")
+    if gtok.dim() != 3 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != gtok.shape[2] or gtok.shape[1] != H * W:
+        raise RuntimeError("conv3x3_input_grad_tokens needs gtok (B, H*W, Cout) and w (Cout, Cin, 3, 3)")
+    B, HW, Cout = gtok.shape
+    Cin = w.shape[1]
+    if Cout % 4:
+        raise RuntimeError("conv3x3_input_grad_tokens needs Cout a multiple of 4")
+    wm = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cin, 9 * Cout).contiguous()
+    out = torch.empty((B, HW, Cin), device=gtok.device, dtype=torch.float32)
+    rc = lib().msm_gemm_f32(_p(gtok), None, _p(wm), None, _p(out), HW, Cin, 9 * Cout, B,
+                            Cout, 1, HW * Cout, 0, 0, Cin, 1, HW * Cin, 0,
+                            2, H, W, Cout, 0, 0, 1, _stream())
+    check(rc, "msm_gemm_f32(conv3x3 input gradient, tokens)")
+    return out
+
+
+def groupnorm_backward(x, gout, stats, gamma, beta, groups=32, *, eps=1e-5, relu=False, splits=None, want_dx=True, want_dgamma=True,
+                       want_dbeta=True):
+    """Backward of groupnorm_tokens (csrc/norm_bwd.hip): x, gout (B, HW, C), stats (B, C, 2) float64 the forward's moments
+    (groupnorm_stats(x)), gamma, beta (C,); ``relu``: the forward applied a ReLU (the mask y > 0 is recomputed, nothing is stored).
+    Returns (dx (B, HW, C), dgamma (C,), dbeta (C,)), None for each one not wanted.  C a multiple of 4 and of ``groups``, at most 256.
+    ``splits``: the number of pixel ranges per image whose partial sums are added in index order (None: ranges of 256 pixels); the
+    result is bit-identical from call to call for a given (shape, splits)."""
+    _c(x, "x"), _c(gout, "gout"), _c(stats, "stats", torch.float64), _c(gamma, "gamma"), _c(beta, "beta")
+    if x.dim() != 3 or gout.shape != x.shape:
+        raise RuntimeError("groupnorm_backward needs x and gout (B, HW, C)")
+    B, HW, C = x.shape
+    groups = int(groups)
+    if tuple(stats.shape) != (B, C, 2) or tuple(gamma.shape) != (C,) or tuple(beta.shape) != (C,):
+        raise RuntimeError("groupnorm_backward needs stats (B, C, 2) float64 and gamma, beta (C,)")
+    if groups < 1 or C % groups or C % 4 or C > 256:
+        raise RuntimeError(f"groupnorm_backward needs C a multiple of 4 and of groups, at most 256 (C={C}, groups={groups})")
+    splits = 0 if splits is None else int(splits)
+    if splits < 0:
+        raise RuntimeError("groupnorm_backward: splits must be None or >= 1")
+    n = lib().msm_groupnorm_bwd_workspace(B, HW, C, groups, splits)
+    if n < 0:
+        check(int(n), "msm_groupnorm_bwd_workspace")
+    ws = torch.empty((n,), device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x) if want_dx else None
+    dg = torch.empty((C,), device=x.device, dtype=torch.float32) if want_dgamma else None
+    db = torch.empty((C,), device=x.device, dtype=torch.float32) if want_dbeta else None
+    rc = lib().msm_groupnorm_bwd_f32(_p(x), _p(gout), _p(stats), _p(gamma), _p(beta), _p(dx), _p(dg), _p(db), _p(ws), B, HW, C, groups,
+                                     float(eps), 1 if relu else 0, splits, _stream())
+    check(rc, "msm_groupnorm_bwd_f32")
+    return dx, dg, db
+
+
+def upsample_bilinear(x, hw, HW):
+    """F.interpolate(size=HW, mode="bilinear", align_corners=False) of a token map x (B, h*w, C) -> (B, H*W, C): the fused add of
+    groupnorm_tokens(up=...) as an operator of its own, same arithmetic (csrc/norm_bwd.hip).  x dense or a token-range slice of a larger
+    buffer (row stride C, any batch stride); C a multiple of 4."""
+    _chk(x, "x")
+    (h, w), (H, W) = (int(hw[0]), int(hw[1])), (int(HW[0]), int(HW[1]))
+    if x.dim() != 3 or x.shape[1] != h * w or min(h, w, H, W) < 1 or x.shape[2] % 4:
+        raise RuntimeError("upsample_bilinear needs x (B, h*w, C) with C a multiple of 4 and h, w, H, W >= 1")
+    B, _, C = x.shape
+    if x.stride(2) != 1 or x.stride(1) != C or (B > 1 and x.stride(0) < h * w * C):
+        raise RuntimeError("upsample_bilinear: x must have strides (>= h*w*C, C, 1)")
+    out = torch.empty((B, H * W, C), device=x.device, dtype=torch.float32)
+    rc = lib().msm_upsample_bilinear_tokens_f32(_p(x), x.stride(0) if B > 1 else 0, _p(out), B, h, w, H, W, C, _stream())
+    check(rc, "msm_upsample_bilinear_tokens_f32")
+    return out
+
+
+def upsample_bilinear_backward(gout, hw, HW):
+    """Adjoint of the bilinear token-map upsampling (csrc/norm_bwd.hip): gout (B, H*W, C) -> (B, h*w, C), C a multiple of 4.  Gather
+    form, no atomics: bit-identical from call to call."""
+    _c(gout, "gout")
+    (h, w), (H, W) = (int(hw[0]), int(hw[1])), (int(HW[0]), int(HW[1]))
+    if gout.dim() != 3 or gout.shape[1] != H * W or min(h, w, H, W) < 1 or gout.shape[2] % 4:
+        raise RuntimeError("upsample_bilinear_backward needs gout (B, H*W, C) with C a multiple of 4 and h, w, H, W >= 1")
+    B, _, C = gout.shape
+    gin = torch.empty((B, h * w, C), device=gout.device, dtype=torch.float32)
+    check(lib().msm_upsample_bilinear_bwd_tokens_f32(_p(gout), _p(gin), B, h, w, H, W, C, _stream()), "msm_upsample_bilinear_bwd_tokens_f32")
+    return gin
+
+
 def layernorm(x, g1, b1, *, parts=None, bias=None, l2norm=False, g2=None, b2=None, eps=1e-5):
     """LayerNorm(x + sum(parts) + bias) [-> unit length] [-> second LayerNorm].  Returns y or (y, y2)."""
     _c(x, "x"), _c(parts, "parts"), _c(bias, "bias"), _c(g1, "g1"), _c(b1, "b1"), _c(g2, "g2"), _c(b2, "b2")

@@ -14,6 +14,12 @@ are torch.autograd.Function wrappers whose forward AND backward run in libmsm_hi
                                     msm_conv3x3_c64_wgrad (weight, bias) and the implicit GEMM on the mirrored taps (input):
                                     ``conv3x3``; with it ``head_forward_train`` / ``head_losses`` train the RGB-D head
                                     (SimpleBasePixelDecoder + the single-level decoder) from the embedding to the loss dict
+    GroupNorm (+ ReLU) on token maps forward msm_groupnorm_stats_f32 + msm_groupnorm_apply_f32; backward msm_groupnorm_bwd_f32 (``group_norm_tokens``)
+    bilinear FPN upsampling         forward msm_upsample_bilinear_tokens_f32; backward its gather-form adjoint (``upsample_bilinear_tokens``)
+    3x3 FPN output convolution      forward msm_conv3x3_c64_f32; backward msm_conv3x3_c64_wgrad with Cout = 64 and the implicit GEMM, on
+                                    tokens in and out: with these ``pixel_decoder_forward_train`` / ``segmentation_head_forward_train`` /
+                                    ``segmentation_head_losses`` train the ResNet-50 head (MSDeformAttnPixelDecoder + the multi-level
+                                    decoder) from the backbone's four feature maps to the loss dict
 
 and the cheap row-local glue (LayerNorm, ReLU, residual adds, L2 normalisation of 256-wide rows: < 1 % of the FLOPs) is left to
 torch's own differentiable elementwise ops on the device tensors.  ``decoder_forward_train`` follows the reference's literal
@@ -57,6 +63,17 @@ def _t2(x):
     return ops.transpose_last2(x.reshape(1, *x.shape))[0]
 
 
+def _gemm_over_rows(a, w):
+    """a (N, R) @ w (K, R)^T -> (N, K) where the reduction runs over R rows of a token map (a weight or bias gradient).  From 4096
+    rows on, the reduction is cut into up to 64 parts of at least 2048 rows (msm_gemm_f32's split_k: the few output tiles of a
+    64 ... 1024-wide layer would otherwise leave most of the chip idle for a 150 000-row reduction) and the parts are added in
+    index order."""
+    parts = min(64, a.shape[-1] // 2048)
+    if parts <= 1:
+        return ops.gemm(a, w)
+    return ops.gemm(a, w, split_k=parts).sum(0)
+
+
 class _Linear(torch.autograd.Function):
     """y = x W^T + b over the last dimension (F.linear, AU:134-140 / DEC:296-300,329-341)."""
 
@@ -78,10 +95,10 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gx = ops.gemm(g2, _t2(w)).view(ctx.in_shape)                      # (M,N) (N,K)
         if ctx.needs_input_grad[1]:
-            gw = ops.gemm(_t2(g2), _t2(x2))                                    # (N,M) (M,K)
+            gw = _gemm_over_rows(_t2(g2), _t2(x2))                             # (N,M) (M,K)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             ones = torch.ones((1, g2.shape[0]), device=g2.device, dtype=torch.float32)
-            gb = ops.gemm(ones, _t2(g2))[0]                                    # column sums on the MFMA path
+            gb = _gemm_over_rows(ones, _t2(g2))[0]                             # column sums on the MFMA path
         return gx, gw, gb
 
 
@@ -273,6 +290,194 @@ def head_forward_train(head, features):
     else:
         mask_features = conv3x3(y, pd.mask_features.weight, pd.mask_features.bias)
     return decoder_forward_train(head.predictor, [y], mask_features)
+
+
+class _GroupNormTokens(torch.autograd.Function):
+    """GroupNorm (+ ReLU) of a token map (B, HW, C): forward ops.groupnorm_stats + ops.groupnorm_tokens, backward
+    msm_groupnorm_bwd_f32 on the saved input and its float64 moments (the ReLU mask is recomputed from them)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps, relu):
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        stats = ops.groupnorm_stats(x)
+        y = ops.groupnorm_tokens(x, gamma, beta, x.shape[1], 1, groups, relu=relu, eps=eps, stats=stats, stats_ready=True)
+        ctx.save_for_backward(x, stats, gamma, beta)
+        ctx.cfg = (int(groups), float(eps), bool(relu))
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stats, gamma, beta = ctx.saved_tensors
+        groups, eps, relu = ctx.cfg
+        need = ctx.needs_input_grad
+        if not any(need[:3]):
+            return None, None, None, None, None, None
+        dx, dg, db = ops.groupnorm_backward(x, g.contiguous(), stats, gamma, beta, groups, eps=eps, relu=relu, want_dx=need[0],
+                                            want_dgamma=need[1], want_dbeta=need[2])
+        return dx, dg, db, None, None, None
+
+
+def group_norm_tokens(x, gamma, beta, groups=32, eps=1e-5, relu=False):
+    """Differentiable GroupNorm (then ReLU when ``relu``) of a token map x (B, HW, C), both passes in libmsm_hip.so: C a multiple
+    of 4 and of ``groups``, at most 256.  A frozen x, gamma or beta gets no gradient (and costs no work)."""
+    return _GroupNormTokens.apply(x, gamma, beta, groups, eps, relu)
+
+
+class _UpsampleBilinearTokens(torch.autograd.Function):
+    """F.interpolate(size=HW, mode="bilinear", align_corners=False) on token maps (msdeformattn.py:349): forward
+    msm_upsample_bilinear_tokens_f32, backward its gather-form adjoint."""
+
+    @staticmethod
+    def forward(ctx, x, hw, HW):
+        C = x.shape[2]
+        if x.stride(2) != 1 or x.stride(1) != C or (x.shape[0] > 1 and x.stride(0) < x.shape[1] * C):
+            x = x.contiguous()
+        ctx.sizes = (tuple(hw), tuple(HW))
+        return ops.upsample_bilinear(x, hw, HW)
+
+    @staticmethod
+    def backward(ctx, g):
+        hw, HW = ctx.sizes
+        return ops.upsample_bilinear_backward(g.contiguous(), hw, HW), None, None
+
+
+def upsample_bilinear_tokens(x, hw, HW):
+    """Differentiable bilinear resize of a token map x (B, h*w, C) from ``hw`` = (h, w) to ``HW`` = (H, W) -> (B, H*W, C)."""
+    return _UpsampleBilinearTokens.apply(x, hw, HW)
+
+
+class _TransposeLast2(torch.autograd.Function):
+    """(B, R, C) -> (B, C, R) contiguous through the library's transpose kernel, in both directions (NCHW planes <-> tokens)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.transpose_last2(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.transpose_last2(g.contiguous())
+
+
+class _Conv3x3Tokens(torch.autograd.Function):
+    """The FPN output convolution (layer_1: 64 -> 64, 3x3 / pad 1, no bias; msdeformattn.py:272-281) on token maps in and out:
+    forward msm_conv3x3_c64_f32, backward msm_conv3x3_c64_wgrad (Cout = 64) and the implicit GEMM on the mirrored taps, both without
+    leaving the token layout (``_Conv3x3`` is the planes-out sibling for the mask_features convolution of the RGB-D head)."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, H, W):
+        if tok.dim() != 3 or tok.shape[2] != 64 or tuple(weight.shape) != (64, 64, 3, 3) or tok.shape[1] != H * W:
+            raise RuntimeError("training: the FPN output convolution needs a (B, H*W, 64) token map and a (64, 64, 3, 3) weight")
+        tok = tok.contiguous()
+        y, _ = ops.conv3x3_c64(tok, weight.permute(0, 2, 3, 1).reshape(64, 576).contiguous(), int(H), int(W))
+        ctx.save_for_backward(tok, weight)
+        ctx.hw = (int(H), int(W))
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        tok, weight = ctx.saved_tensors
+        H, W = ctx.hw
+        g = g.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.conv3x3_input_grad_tokens(g, weight, H, W)
+        if ctx.needs_input_grad[1]:
+            dw, _ = ops.conv3x3_weight_grad(tok, ops.transpose_last2(g), H, W, want_bias=False)
+            gw = dw.view(64, 3, 3, 64).permute(0, 3, 1, 2).contiguous()                   # tap-major -> (64, 64, 3, 3)
+        return gx, gw, None, None
+
+
+def _encoder_layer(layer, src, pos, ref, norm_wh, ss, starts):
+    """MSDeformAttnTransformerEncoderLayer.forward (msdeformattn.py:116-131) with MSDeformAttn.forward (ms_deform_attn.py:95-125)
+    written out: the projections are ``linear``, the core MSDeformAttnFunction; the softmax over the L * P logits and the location
+    arithmetic (:101-109) are torch's row-local ops."""
+    a = layer.self_attn
+    B, S, C = src.shape
+    M, L, P = a.n_heads, a.n_levels, a.n_points
+    q = src + pos
+    value = linear(src, a.value_proj.weight, a.value_proj.bias).view(B, S, M, C // M)
+    off = linear(q, a.sampling_offsets.weight, a.sampling_offsets.bias).view(B, S, M, L, P, 2)
+    aw = F.softmax(linear(q, a.attention_weights.weight, a.attention_weights.bias).view(B, S, M, L * P), -1).view(B, S, M, L, P)
+    loc = ref[None, :, None, None, None, :] + off / norm_wh[None, None, None, :, None, :]
+    o = MSDeformAttnFunction.apply(value, ss, starts, loc, aw, a.im2col_step)
+    src = F.layer_norm(src + linear(o, a.output_proj.weight, a.output_proj.bias), (C,), layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
+    f = linear(F.relu(linear(src, layer.linear1.weight, layer.linear1.bias)), layer.linear2.weight, layer.linear2.bias)
+    return F.layer_norm(src + f, (C,), layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
+
+
+def pixel_decoder_forward_train(pd, features):
+    """Differentiable MSDeformAttnPixelDecoder.forward_features (msdeformattn.py:315-358) in the reference's literal order, for
+    ``pd`` = modeling.MSDeformAttnPixelDecoder and ``features`` {"res2".."res5": (B, C_l, H_l, W_l)}: input projections (1x1
+    convolution as ``linear`` on tokens, GroupNorm), sine position + level_embed (:61-85), the encoder layers, the per-level split,
+    the res2 FPN step (lateral 1x1 + GroupNorm, + bilinear upsample, 3x3 output convolution + GroupNorm + ReLU) and the 1x1
+    mask_features convolution.  Returns (mask_features (B, mask_dim, H, W), transformer_encoder_features, multi_scale_features) as
+    forward_features does; gradients reach every parameter of ``pd`` and the four feature maps.  Heavy operators run in
+    libmsm_hip.so in both directions (GEMMs, MSDeformAttn core, GroupNorm, upsampling, 3x3 convolution, transposes); LayerNorm over
+    the conv_dim-wide rows, the softmax over L * P logits, ReLU and the adds are torch's.  Neither the inference ``forward_features`` nor
+    any cache of ``pd`` is touched.  fp32; conv_dim 64 (the 3x3 kernels), DROPOUT 0 (every shipped yaml)."""
+    if getattr(pd, "transformer_dropout", 0.0) > 0:
+        raise NotImplementedError("pixel_decoder_forward_train: transformer dropout > 0 is not implemented (every shipped yaml has DROPOUT: 0.0)")
+    C = pd.conv_dim
+    if C != 64:
+        raise NotImplementedError("pixel_decoder_forward_train: the 3x3 convolution backward needs conv_dim == 64")
+    names = pd.transformer_in_features[::-1]                                              # res5, res4, res3
+    dev = features[names[0]].device
+    B = features[names[0]].shape[0]
+    toks, pos, ref, shapes = [], [], [], []
+    for idx, f in enumerate(names):
+        x = features[f].float()
+        h, w = int(x.shape[2]), int(x.shape[3])
+        shapes.append((h, w))
+        conv, gn = pd.input_proj[idx][0], pd.input_proj[idx][1]
+        t = linear(_TransposeLast2.apply(x.reshape(B, x.shape[1], h * w)), conv.weight.view(C, -1), conv.bias)
+        toks.append(group_norm_tokens(t, gn.weight, gn.bias, gn.num_groups, gn.eps))
+        pos.append(ops.pos_embed_sine(h, w, pd.pe_layer.num_pos_feats, dev, layout="tokens") + pd.transformer.level_embed[idx])   # :75
+        ys = (torch.arange(h, device=dev, dtype=torch.float32) + 0.5) / h                  # pixel centres, valid ratio 1 (:141-153)
+        xs = (torch.arange(w, device=dev, dtype=torch.float32) + 0.5) / w
+        ref.append(torch.stack([xs[None, :].expand(h, w), ys[:, None].expand(h, w)], -1).reshape(h * w, 2))
+    src = torch.cat(toks, 1)
+    pos, ref = torch.cat(pos, 0), torch.cat(ref, 0)
+    sizes = [h * w for h, w in shapes]
+    starts_host = [sum(sizes[:i]) for i in range(len(sizes))]
+    ss = torch.tensor(shapes, dtype=torch.int64, device=dev)
+    starts = torch.tensor(starts_host, dtype=torch.int64, device=dev)
+    norm_wh = torch.tensor([[w, h] for h, w in shapes], dtype=torch.float32, device=dev)   # ms_deform_attn.py:104
+    for layer in pd.transformer.encoder.layers:
+        src = _encoder_layer(layer, src, pos, ref, norm_wh, ss, starts)
+    levels = [src[:, o:o + n] for o, n in zip(starts_host, sizes)]                        # (B, h*w, C) token ranges
+    out = [z.transpose(1, 2).view(B, C, h, w) for z, (h, w) in zip(levels, shapes)]       # NCHW-shaped views, as forward_features returns
+    # the one FPN level on res2 (:343-351)
+    x = features[pd.in_features[0]].float()
+    H, W = int(x.shape[2]), int(x.shape[3])
+    lat = linear(_TransposeLast2.apply(x.reshape(B, x.shape[1], H * W)), pd.adapter_1.weight.view(C, -1), None)
+    an, ln = pd.adapter_1.norm, pd.layer_1.norm
+    y = group_norm_tokens(lat, an.weight, an.bias, an.num_groups, an.eps) + upsample_bilinear_tokens(levels[-1], shapes[-1], (H, W))
+    y = _Conv3x3Tokens.apply(y, pd.layer_1.weight, H, W)
+    y = group_norm_tokens(y, ln.weight, ln.bias, ln.num_groups, ln.eps, relu=True)
+    out.append(_TransposeLast2.apply(y).view(B, C, H, W))
+    mf = linear(y, pd.mask_features.weight.view(pd.mask_dim, C), pd.mask_features.bias)
+    mask_features = _TransposeLast2.apply(mf).view(B, pd.mask_dim, H, W)
+    return mask_features, out[0], out[:pd.maskformer_num_feature_levels]
+
+
+def segmentation_head_forward_train(head, features):
+    """Differentiable MeanShiftMaskFormerHead.layers for the ResNet-50 configuration (meanshift_former_head.py:121-126):
+    pixel_decoder_forward_train, then decoder_forward_train on its multi-scale features and mask features.  Returns
+    {"pred_logits", "pred_masks", "aux_outputs"}; gradients reach every parameter of the head and the backbone feature maps.
+    (The RGB-D head, whose pixel decoder is SimpleBasePixelDecoder, is ``head_forward_train``'s.)"""
+    from .modeling import MSDeformAttnPixelDecoder
+    pd = head.pixel_decoder
+    if not isinstance(pd, MSDeformAttnPixelDecoder):
+        raise NotImplementedError(f"segmentation_head_forward_train: {type(pd).__name__} is not MSDeformAttnPixelDecoder; "
+                                  "head_forward_train trains the SimpleBasePixelDecoder head")
+    mask_features, _, multi_scale_features = pixel_decoder_forward_train(pd, features)
+    return decoder_forward_train(head.predictor, multi_scale_features, mask_features)
+
+
+def segmentation_head_losses(head, features, targets, criterion):
+    """One training step of the ResNet-50 head from the backbone's feature maps to the weighted loss dict
+    (tabletop_train_net_pretrained.py:209-246): segmentation_head_forward_train -> ``criterion`` -> weighted_losses."""
+    return weighted_losses(criterion(segmentation_head_forward_train(head, features), targets), criterion.weight_dict)
 
 
 def weighted_losses(losses, weight_dict):
