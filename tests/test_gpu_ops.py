@@ -12,6 +12,7 @@ from oracle import msm_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import attn_cases  # noqa: E402
 import dec_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -369,7 +370,10 @@ def test_hypersphere_attention_low_precision(B, Lq, S, masked, kv_bf16):
               keys_f16=f16keys or f16scores)
     got = ops().hypersphere_attention(q.to(DEV), kd, vd, H, low_precision=True, **kw)
     err = (got.cpu() - ref).abs()
-    print(f"lp attention S={S} kv_bf16={kv_bf16}: max |d| {float(err.max()):.2e} mean {float(err.mean()):.2e}")
+    form = "lp2" if f16keys else ("lp3" if f16scores else ("lp1" if kv_bf16 is True else "lp0"))
+    rt = attn_cases.route(form, B, Lq, S, H, masked)              # fp32 K / V with S <= 128 stay on the fp32 kernel: operand f32
+    print(f"lp attention S={S} kv_bf16={kv_bf16}: max |d| {float(err.max()):.2e} mean {float(err.mean()):.2e}"
+          f" [route {attn_cases.path(rt)} mm={rt.mm} ns={rt.ns} operand {rt.operand}{' (the fp32 kernel)' if rt.fallback else ''}]")
     if f16keys or f16scores:
         assert float(err.max()) < 1.5e-2 and float(err.mean()) < 8e-4
     assert float(err.max()) < 3e-2 and float(err.mean()) < 2e-3

@@ -728,7 +728,8 @@ def mask_logits(mask_embed, mask_features, *, want_mask=True, target_size=None, 
 
 def hypersphere_attention(q, k, v, heads, *, masked=None, row_any=None, kappa=KAPPA, low_precision=False, keys_f16=False):
     """q (B,Lq,E), k/v (B,S,E) already projected (last dim contiguous, may be column slices of a
-    wider buffer); masked uint8 (B,Lq,S).  Returns (B,Lq,E).
+    wider buffer); masked uint8 (B,Lq,S): ANY nonzero byte means masked (1, 2, 128, 255 alike); row_any int32 (B,Lq): 0 switches a row's
+    mask off (a fully masked row attends everywhere).  Returns (B,Lq,E).
     low_precision (or bf16 k / v): bf16 MFMA operands with fp32 accumulation (msm_hypersphere_attn_lp_fwd); k and v may then be
     torch.bfloat16 (as written by kv_project_multi(..., out_dtype=torch.bfloat16)) or float32.
     keys_f16 (precision "f16"): q^ / k^ enter the score MFMAs as IEEE halves; a 16-bit k then holds HALF bit patterns (the K columns
@@ -844,7 +845,7 @@ def hypersphere_attention_fused_kv(q, x_f16, w_packed, rowcol, col_v_t, size, he
     """Cross attention over a long key sequence with the folded K/V projection inside the kernel (msm_hypersphere_attn_fused_kv_fwd;
     16-bit plans): q (B, Lq, E) projected queries; x_f16 = tokens_f16(level feature) (B, H*W, 64); w_packed = attn_pack_kv_weights(w);
     rowcol (H + W, 2E) the separable constants of kv_project(cmat_width=W); col_v_t (E, W) = rowcol[H:, E:].t(); size = (H, W), W % 16 == 0.
-    masked: uint8 (B, Lq, S), packed here, or the int16 bit-packed form (attn_pack_mask_bits / attn_mask_pooled(bits=True)).
+    masked: uint8 (B, Lq, S), any nonzero byte = masked, packed here, or the int16 bit-packed form (attn_pack_mask_bits / attn_mask_pooled(bits=True)).
     keys_f16: q^ / k^ as IEEE halves (precision "f16") instead of bf16.  Returns (B, Lq, E)."""
     _chk(q, "q"), _c(x_f16, "x_f16", torch.float16), _c(w_packed, "w_packed", torch.float16), _c(rowcol, "rowcol"), _c(col_v_t, "col_v_t")
     prepacked = masked is not None and masked.dtype == torch.int16            # attn_mask_pooled(bits=True) / attn_pack_mask_bits output
