@@ -1,0 +1,244 @@
+// Full-model-clipped AdamW over a device-resident table of tensors (see include/msm_hip.h: msm_optim_grad_norm,
+// msm_optim_adamw_step, msm_optim_zero).  Reference: Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191 --
+// torch.nn.utils.clip_grad_norm_ over every parameter followed by torch.optim.AdamW with one param group per tensor.
+//
+// The table cuts every tensor into chunks of OPT_CHUNK elements (a 3-element bias is one chunk, a 524 288-element weight 64), and a
+// launch is one workgroup per chunk, whatever the number of tensors:
+//   norm    workgroup c: sum of g^2 over its chunk, in double -> partials[c]; workgroup 0 also advances the call counter
+//   step    workgroup c: adds partials[0 .. n_chunks) (thread t takes t, t + 256, ... in ascending order, then a fixed tree over the
+//           256 threads: every workgroup forms the same bits), total_norm and coef from it, then the AdamW update of its chunk
+//   zero    workgroup c: g = 0 over its chunk
+// A third launch that sums the partials once would save every workgroup n_chunks L2 reads of 8 bytes (about 17 KiB for the 298
+// tensors of the ResNet-50 head, against the 288 KiB of HBM traffic of a full chunk) and cost a launch and a dependent kernel
+// boundary on a step that is two launches and 0.1 ms long.
+// The counter is written by the norm launch (or the one-thread tick launch that stands in for it when nothing is clipped) and only
+// read by the step launch behind it on the stream.  No atomics, no hand-off between workgroups: bit-identical from call to call
+// for a given table.
+#include "common.h"
+
+namespace msm {
+
+constexpr int OPT_T = 256;                  // threads per workgroup
+constexpr int OPT_CHUNK = MSM_OPTIM_CHUNK;  // elements per chunk (a multiple of 4 OPT_T: whole float4 rounds)
+constexpr int OPT_REC = 8;                  // int64 per tensor record
+constexpr int OPT_HYP = 8;                  // doubles per hyper-parameter row
+static_assert(OPT_CHUNK % (4 * OPT_T) == 0, "a chunk is whole float4 rounds of the workgroup");
+
+struct OptChunk {
+    float *p, *g, *m, *v;
+    int n;                                  // elements of this chunk (0: a record the kernel refuses)
+    int row;
+    bool vec;                               // 16-byte accesses
+};
+
+// chunk c of the table.  A tensor index, an offset or a row outside the table gives n = 0: the table is written by the host, and a
+// stale or torn one must end as a skipped chunk, not as a wild access.
+__device__ __forceinline__ OptChunk opt_chunk(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks, int c, int n_tensors,
+                                              int n_rows, int64_t align_bit) {
+    OptChunk k;
+    const int64_t t = chunks[2 * (int64_t)c], off = chunks[2 * (int64_t)c + 1];
+    k.n = 0;
+    k.row = 0;
+    k.vec = false;
+    k.p = k.g = k.m = k.v = nullptr;
+    if (t < 0 || t >= n_tensors) return k;
+    const int64_t* r = tensors + t * OPT_REC;
+    const int64_t numel = r[4], row = r[5];
+    if (off < 0 || off >= numel || (off & 3) || row < 0 || row >= n_rows) return k;
+    k.p = reinterpret_cast<float*>(r[0]) + off;
+    k.g = reinterpret_cast<float*>(r[1]) + off;
+    k.m = reinterpret_cast<float*>(r[2]) + off;
+    k.v = reinterpret_cast<float*>(r[3]) + off;
+    k.n = (int)min((int64_t)OPT_CHUNK, numel - off);
+    k.row = (int)row;
+    k.vec = (r[6] & align_bit) != 0;
+    return k;
+}
+
+// sum over the workgroup in a fixed tree; every thread gets it
+__device__ __forceinline__ double opt_block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = OPT_T / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(OPT_T) void optim_grad_norm_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks,
+                                                                double* __restrict__ partials, int64_t* __restrict__ state, int n_tensors) {
+    __shared__ double red[OPT_T];
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, INT32_MAX, MSM_OPTIM_ALIGNED_G);
+    double acc = 0.0;
+    if (k.vec) {
+        const int n4 = k.n & ~3;
+        for (int i = tid * 4; i < n4; i += OPT_T * 4) {
+            const float4 g = *reinterpret_cast<const float4*>(k.g + i);
+            acc = fma((double)g.x, (double)g.x, acc);
+            acc = fma((double)g.y, (double)g.y, acc);
+            acc = fma((double)g.z, (double)g.z, acc);
+            acc = fma((double)g.w, (double)g.w, acc);
+        }
+        if (n4 + tid < k.n) acc = fma((double)k.g[n4 + tid], (double)k.g[n4 + tid], acc);
+    } else {
+        for (int i = tid; i < k.n; i += OPT_T) acc = fma((double)k.g[i], (double)k.g[i], acc);
+    }
+    const double s = opt_block_sum(acc, red);
+    if (tid == 0) {
+        partials[c] = s;
+        if (c == 0) state[0] += 1;
+    }
+}
+
+__global__ void optim_tick_kernel(int64_t* __restrict__ state) { state[0] += 1; }
+
+struct OptScalars {
+    float coef, decay, w1, b2, w2, bc2s, eps, step_size;
+};
+
+__device__ __forceinline__ void opt_update(float& p, float& g, float& m, float& v, const OptScalars& s, bool clip) {
+    if (clip) g *= s.coef;
+    p *= s.decay;
+    m += (g - m) * s.w1;
+    v = v * s.b2 + s.w2 * g * g;
+    p -= s.step_size * (m / (sqrtf(v) / s.bc2s + s.eps));
+}
+
+__global__ __launch_bounds__(OPT_T) void optim_adamw_step_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks,
+                                                                 const double* __restrict__ hyper, const double* __restrict__ partials,
+                                                                 int64_t* __restrict__ state, int n_tensors, int n_chunks, int n_rows,
+                                                                 float max_norm) {
+    __shared__ double red[OPT_T];
+    __shared__ OptScalars sh;
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, n_rows, MSM_OPTIM_ALIGNED);
+    double total = 0.0, coef = 1.0;
+    if (max_norm > 0.f) {
+        double a = 0.0;
+        for (int j = tid; j < n_chunks; j += OPT_T) a += partials[j];
+        total = sqrt(opt_block_sum(a, red));
+        const double q = (double)max_norm / (total + 1e-6);
+        coef = q > 1.0 ? 1.0 : q;               // a nan norm stays a nan coefficient, as torch's clamp(max=1) leaves it
+    }
+    if (tid == 0) {
+        const double* h = hyper + (int64_t)k.row * OPT_HYP;
+        const double lr = h[0], wd = h[1], b1 = h[2], b2 = h[3], eps = h[4];
+        const double step = (double)(state[0] - (int64_t)h[5]);
+        const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+        OptScalars s;
+        s.coef = (float)coef;
+        s.decay = (float)(1.0 - lr * wd);
+        s.w1 = (float)(1.0 - b1);
+        s.b2 = (float)b2;
+        s.w2 = (float)(1.0 - b2);
+        s.bc2s = (float)sqrt(bc2);
+        s.eps = (float)eps;
+        s.step_size = (float)(lr / bc1);
+        sh = s;
+        if (c == 0) {
+            float* out = reinterpret_cast<float*>(state + 1);
+            out[0] = (float)total;
+            out[1] = s.coef;
+        }
+    }
+    __syncthreads();
+    const OptScalars s = sh;
+    const bool clip = s.coef != 1.f;            // coef == 1 leaves every g as it is: no store
+    if (k.vec) {
+        const int n4 = k.n & ~3;
+        for (int i = tid * 4; i < n4; i += OPT_T * 4) {
+            float4 p = *reinterpret_cast<const float4*>(k.p + i), g = *reinterpret_cast<const float4*>(k.g + i);
+            float4 m = *reinterpret_cast<const float4*>(k.m + i), v = *reinterpret_cast<const float4*>(k.v + i);
+            opt_update(p.x, g.x, m.x, v.x, s, clip);
+            opt_update(p.y, g.y, m.y, v.y, s, clip);
+            opt_update(p.z, g.z, m.z, v.z, s, clip);
+            opt_update(p.w, g.w, m.w, v.w, s, clip);
+            *reinterpret_cast<float4*>(k.p + i) = p;
+            *reinterpret_cast<float4*>(k.m + i) = m;
+            *reinterpret_cast<float4*>(k.v + i) = v;
+            if (clip) *reinterpret_cast<float4*>(k.g + i) = g;
+        }
+        const int i = n4 + tid;
+        if (i < k.n) {
+            float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
+            opt_update(p, g, m, v, s, clip);
+            k.p[i] = p, k.m[i] = m, k.v[i] = v;
+            if (clip) k.g[i] = g;
+        }
+    } else {
+        for (int i = tid; i < k.n; i += OPT_T) {
+            float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
+            opt_update(p, g, m, v, s, clip);
+            k.p[i] = p, k.m[i] = m, k.v[i] = v;
+            if (clip) k.g[i] = g;
+        }
+    }
+}
+
+__global__ __launch_bounds__(OPT_T) void optim_zero_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks, int n_tensors) {
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, INT32_MAX, MSM_OPTIM_ALIGNED_G);
+    if (k.vec) {
+        const int n4 = k.n & ~3;
+        for (int i = tid * 4; i < n4; i += OPT_T * 4) *reinterpret_cast<float4*>(k.g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n4 + tid < k.n) k.g[n4 + tid] = 0.f;
+    } else {
+        for (int i = tid; i < k.n; i += OPT_T) k.g[i] = 0.f;
+    }
+}
+
+static bool opt_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+}  // namespace msm
+
+using namespace msm;
+
+extern "C" int msm_optim_chunk(void) { return OPT_CHUNK; }
+
+extern "C" int msm_optim_grad_norm(const int64_t* tensors, const int64_t* chunks, double* partials, int64_t* state, int n_tensors,
+                                   int n_chunks, void* stream) {
+    MSM_REQUIRE(tensors && chunks && partials && state, "msm_optim_grad_norm: null pointer");
+    MSM_REQUIRE(opt_aligned8(tensors) && opt_aligned8(chunks) && opt_aligned8(partials) && opt_aligned8(state),
+                "msm_optim_grad_norm: the tables, the partials and the state block must be 8-byte aligned");
+    MSM_REQUIRE(n_tensors >= 1 && n_chunks >= n_tensors, "msm_optim_grad_norm: n_tensors = %d, n_chunks = %d (every tensor has a chunk)",
+                n_tensors, n_chunks);
+    optim_grad_norm_kernel<<<n_chunks, OPT_T, 0, (hipStream_t)stream>>>(tensors, chunks, partials, state, n_tensors);
+    MSM_CHECK_LAUNCH("msm_optim_grad_norm");
+    return MSM_OK;
+}
+
+extern "C" int msm_optim_adamw_step(const int64_t* tensors, const int64_t* chunks, const double* hyper, const double* partials,
+                                    int64_t* state, int n_tensors, int n_chunks, int n_rows, float max_norm, void* stream) {
+    MSM_REQUIRE(tensors && chunks && hyper && state, "msm_optim_adamw_step: null pointer");
+    MSM_REQUIRE(!(max_norm > 0.f) || partials, "msm_optim_adamw_step: max_norm > 0 needs the partials of msm_optim_grad_norm");
+    MSM_REQUIRE(opt_aligned8(tensors) && opt_aligned8(chunks) && opt_aligned8(hyper) && opt_aligned8(partials) && opt_aligned8(state),
+                "msm_optim_adamw_step: the tables, the partials and the state block must be 8-byte aligned");
+    MSM_REQUIRE(n_tensors >= 1 && n_chunks >= n_tensors && n_rows >= 1,
+                "msm_optim_adamw_step: n_tensors = %d, n_chunks = %d, n_rows = %d (every tensor has a chunk and a row)", n_tensors, n_chunks,
+                n_rows);
+    MSM_REQUIRE(max_norm == max_norm, "msm_optim_adamw_step: max_norm is nan");
+    if (!(max_norm > 0.f)) {
+        optim_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(state);
+        MSM_CHECK_LAUNCH("msm_optim_adamw_step(counter)");
+    }
+    optim_adamw_step_kernel<<<n_chunks, OPT_T, 0, (hipStream_t)stream>>>(tensors, chunks, hyper, partials, state, n_tensors, n_chunks,
+                                                                        n_rows, max_norm);
+    MSM_CHECK_LAUNCH("msm_optim_adamw_step");
+    return MSM_OK;
+}
+
+extern "C" int msm_optim_zero(const int64_t* tensors, const int64_t* chunks, int n_tensors, int n_chunks, void* stream) {
+    MSM_REQUIRE(tensors && chunks, "msm_optim_zero: null pointer");
+    MSM_REQUIRE(opt_aligned8(tensors) && opt_aligned8(chunks), "msm_optim_zero: the tables must be 8-byte aligned");
+    MSM_REQUIRE(n_tensors >= 1 && n_chunks >= n_tensors, "msm_optim_zero: n_tensors = %d, n_chunks = %d (every tensor has a chunk)", n_tensors,
+                n_chunks);
+    optim_zero_kernel<<<n_chunks, OPT_T, 0, (hipStream_t)stream>>>(tensors, chunks, n_tensors);
+    MSM_CHECK_LAUNCH("msm_optim_zero");
+    return MSM_OK;
+}

@@ -1860,6 +1860,55 @@ def embloss_info(info, B):
     return dict(K=info[0], status=info[1], flag=info[2], n=info[4:4 + B * Kt].view(B, Kt), N=info[4 + B * Kt:].view(B, Kt))
 
 
+# ---- optimizer (optim.py): full-model-clipped AdamW over a device-resident table of tensors ----
+OPTIM_REC = 8           # int64 per tensor record: p, g, exp_avg, exp_avg_sq addresses, numel, hyper row, flags, 0
+OPTIM_HYP = 8           # doubles per hyper-parameter row: lr, weight_decay, beta1, beta2, eps, step offset, 0, 0
+OPTIM_ALIGNED = 1       # MSM_OPTIM_ALIGNED: p, g, exp_avg and exp_avg_sq are all 16-byte aligned
+OPTIM_ALIGNED_G = 2     # MSM_OPTIM_ALIGNED_G: g is
+
+
+def optim_chunk():
+    """MSM_OPTIM_CHUNK: the elements of one chunk of the optimizer's chunk list (one workgroup's work)."""
+    return int(lib().msm_optim_chunk())
+
+
+def _optim_tables(tensors, chunks, n_tensors, n_chunks):
+    _c(tensors, "tensors", torch.int64), _c(chunks, "chunks", torch.int64)
+    if n_tensors < 1 or tensors.numel() < n_tensors * OPTIM_REC or n_chunks < n_tensors or chunks.numel() < 2 * n_chunks:
+        raise RuntimeError(f"optimizer tables: {n_tensors} records need {n_tensors * OPTIM_REC} int64 (got {tensors.numel()}), "
+                           f"{n_chunks} chunks need {2 * n_chunks} (got {chunks.numel()}), every tensor has a chunk")
+
+
+def optim_grad_norm(tensors, chunks, partials, state, n_tensors, n_chunks):
+    """msm_optim_grad_norm: partials[c] = sum of g^2 over chunk c (double) and state[0] += 1, one launch.  tensors / chunks: int64
+    device tables in the layout of include/msm_hip.h, partials float64 (n_chunks,), state int64 (2,)."""
+    _optim_tables(tensors, chunks, n_tensors, n_chunks)
+    _c(partials, "partials", torch.float64), _c(state, "state", torch.int64)
+    if partials.numel() < n_chunks or state.numel() < 2:
+        raise RuntimeError(f"optim_grad_norm: partials needs {n_chunks} doubles (got {partials.numel()}), state 2 int64")
+    check(lib().msm_optim_grad_norm(_p(tensors), _p(chunks), _p(partials), _p(state), n_tensors, n_chunks, _stream()),
+          "msm_optim_grad_norm")
+
+
+def optim_adamw_step(tensors, chunks, hyper, partials, state, n_tensors, n_chunks, n_rows, max_norm):
+    """msm_optim_adamw_step: clip coefficient from the partials of optim_grad_norm (max_norm > 0; else no clipping, partials may be
+    None and the call advances the counter itself) and torch's AdamW on every chunk, one launch.  hyper float64 (n_rows, 8)."""
+    _optim_tables(tensors, chunks, n_tensors, n_chunks)
+    _c(hyper, "hyper", torch.float64), _c(partials, "partials", torch.float64), _c(state, "state", torch.int64)
+    if n_rows < 1 or hyper.numel() < n_rows * OPTIM_HYP or state.numel() < 2 or (
+            max_norm > 0 and (partials is None or partials.numel() < n_chunks)):
+        raise RuntimeError(f"optim_adamw_step: {n_rows} rows need {n_rows * OPTIM_HYP} doubles (got {hyper.numel()}), state 2 int64, "
+                           f"max_norm > 0 partials of {n_chunks} doubles")
+    check(lib().msm_optim_adamw_step(_p(tensors), _p(chunks), _p(hyper), _p(partials), _p(state), n_tensors, n_chunks, n_rows,
+                                     float(max_norm), _stream()), "msm_optim_adamw_step")
+
+
+def optim_zero(tensors, chunks, n_tensors, n_chunks):
+    """msm_optim_zero: g = 0 for every chunk of the table, one launch."""
+    _optim_tables(tensors, chunks, n_tensors, n_chunks)
+    check(lib().msm_optim_zero(_p(tensors), _p(chunks), n_tensors, n_chunks, _stream()), "msm_optim_zero")
+
+
 def crop_resize(rgb, depth, labels, table, size):
     """ROI crops of a batch of frames in one launch (msm_crop_resize): rgb / depth (F,3,H,W), labels (F,H,W) float, table (N,8)
     int32 rows (frame, label, x0, y0, x1, y1, 0, 0) -> (rgb_crops (N,3,S,S), mask_crops (N,S,S), depth_crops or None)."""
