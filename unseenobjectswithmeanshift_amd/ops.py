@@ -2071,6 +2071,31 @@ def ucn_embedding_tail(a, b=None, size=None, norms=1, eps=1e-12):
     return out
 
 
+def ucn_embedding_tail_bwd(a, b, gout, norms=1, eps=1e-12):
+    """Backward of ``ucn_embedding_tail`` (msm_ucn_embedding_tail_bwd): a, b (B, 64, h, w) fp32 maps of the two towers as the forward took
+    them (b None: one tower), gout (B, 64, H, W) fp32 contiguous -> gin (B, 64, h, w) fp32 channels_last, the gradient of a and of b alike
+    (add fusion).  Deterministic: the same bits at every call."""
+    if a.dtype != torch.float32 or not a.is_cuda or a.dim() != 4 or a.shape[1] != 64:
+        raise RuntimeError("ucn_embedding_tail_bwd: (B, 64, h, w) float32 maps on the GPU")
+    a = a if a.is_contiguous(memory_format=torch.channels_last) else a.contiguous(memory_format=torch.channels_last)
+    if b is not None:
+        if b.shape != a.shape or b.dtype != a.dtype or b.device != a.device:
+            raise RuntimeError("ucn_embedding_tail_bwd: the two towers' maps must match")
+        b = b if b.is_contiguous(memory_format=torch.channels_last) else b.contiguous(memory_format=torch.channels_last)
+    B, _, h, w = a.shape
+    if gout.dim() != 4 or gout.shape[0] != B or gout.shape[1] != 64 or gout.dtype != torch.float32 or gout.device != a.device:
+        raise RuntimeError("ucn_embedding_tail_bwd: gout must be a (B, 64, H, W) float32 map on the towers' device")
+    _c(gout, "gout")
+    H, W = int(gout.shape[2]), int(gout.shape[3])
+    n = lib().msm_ucn_embedding_tail_bwd_workspace(B, H, w)
+    check(min(n, 0), "msm_ucn_embedding_tail_bwd_workspace")
+    ws = torch.empty(n, device=a.device, dtype=torch.float32)
+    gin = torch.empty((B, 64, h, w), device=a.device, dtype=torch.float32, memory_format=torch.channels_last)
+    check(lib().msm_ucn_embedding_tail_bwd(_p(a), _p(b), _p(gout), _p(gin), _p(ws), n, B, h, w, H, W, int(norms), float(eps), _stream()),
+          "msm_ucn_embedding_tail_bwd")
+    return gin
+
+
 def to_f16(t):
     """fp32 -> fp16 (round to nearest even, clamped to the half range) on the HIP path (msm_f32_to_f16)."""
     _c(t, "t")

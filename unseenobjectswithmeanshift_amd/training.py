@@ -20,6 +20,11 @@ are torch.autograd.Function wrappers whose forward AND backward run in libmsm_hi
                                     tokens in and out: with these ``pixel_decoder_forward_train`` / ``segmentation_head_forward_train`` /
                                     ``segmentation_head_losses`` train the ResNet-50 head (MSDeformAttnPixelDecoder + the multi-level
                                     decoder) from the backbone's four feature maps to the loss dict
+    UCN embedding tail              forward msm_ucn_embedding_tail (x8 bilinear upsampling of both towers, add fusion, one or two channel
+                                    normalisations in one pass); backward msm_ucn_embedding_tail_bwd (two launches, fixed summation
+                                    order): ``ucn_embedding_tail``; with it and the towers' own modules under torch autograd (stock
+                                    convolutions: MIOpen) ``ucn_towers_forward_train`` / ``ucn_backbone_forward_train`` /
+                                    ``ucn_model_losses`` train the RGB-D model from images
 
 and the cheap row-local glue (LayerNorm, ReLU, residual adds, L2 normalisation of 256-wide rows: < 1 % of the FLOPs) is left to
 torch's own differentiable elementwise ops on the device tensors.  ``decoder_forward_train`` follows the reference's literal
@@ -491,6 +496,17 @@ def decoder_losses(dec, x, mask_features, targets, criterion):
     return weighted_losses(criterion(decoder_forward_train(dec, x, mask_features), targets), criterion.weight_dict)
 
 
+def _head_losses_normalised(head, norm, targets, criterion, labels, embedding_loss, embedding_weight):
+    """head_losses after its normalisation: ``norm`` (B, 64, H, W) is the channel-normalised embedding."""
+    outputs = head_forward_train(head, {head.pixel_decoder.in_features[0]: norm})
+    losses = criterion(outputs, targets)
+    weights = dict(criterion.weight_dict)
+    if embedding_loss is not None:
+        losses["embedding_loss"] = embedding_loss(norm, labels)[0]
+        weights["embedding_loss"] = embedding_weight
+    return weighted_losses(losses, weights)
+
+
 def head_losses(head, embedding, targets, criterion, *, labels=None, embedding_loss=None, embedding_weight=None):
     """The training branch of the RGB-D meta-arch (pretrained_meanshiftformer_model.py:298-333) from the backbone's embedding
     (B, 64, H, W) to the weighted loss dict: F.normalize over channels (once), head_forward_train, ``criterion``, and -- with
@@ -500,10 +516,114 @@ def head_losses(head, embedding, targets, criterion, *, labels=None, embedding_l
     if embedding_loss is not None and (labels is None or embedding_weight is None):
         raise ValueError("head_losses: embedding_loss needs labels and embedding_weight")
     norm = F.normalize(embedding, p=2, dim=1)
-    outputs = head_forward_train(head, {head.pixel_decoder.in_features[0]: norm})
-    losses = criterion(outputs, targets)
-    weights = dict(criterion.weight_dict)
-    if embedding_loss is not None:
-        losses["embedding_loss"] = embedding_loss(norm, labels)[0]
-        weights["embedding_loss"] = embedding_weight
-    return weighted_losses(losses, weights)
+    return _head_losses_normalised(head, norm, targets, criterion, labels, embedding_loss, embedding_weight)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the UCN RGB-D backbone under autograd (lib/fcn/train.py:37-76 trains it against EmbeddingLoss; the RGB-D meta-arch leaves it
+# unfrozen, pretrained_meanshiftformer_model.py:150-152)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _tail_torch(a, b, size, norms, eps):
+    """The definition of the embedding tail: nn.functional.upsample_bilinear of each tower, add fusion, F.normalize ``norms`` times
+    (resnet_dilated.py:325, SEG.py:104-114, pretrained_meanshiftformer_model.py:298)."""
+    u = F.interpolate(a, size=size, mode="bilinear", align_corners=True)
+    if b is not None:
+        u = u + F.interpolate(b, size=size, mode="bilinear", align_corners=True)
+    for _ in range(norms):
+        u = F.normalize(u, p=2, dim=1, eps=eps)
+    return u
+
+
+class _UCNEmbeddingTail(torch.autograd.Function):
+    """ops.ucn_embedding_tail forward, msm_ucn_embedding_tail_bwd backward (u and the normalised vectors are recomputed from the
+    saved low-resolution maps; the full-resolution output is not kept for the backward)."""
+
+    @staticmethod
+    def forward(ctx, a, b, size, norms, eps):
+        cl = lambda t: t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+        a = cl(a)
+        b = None if b is None else cl(b)
+        ctx.save_for_backward(a, b)
+        ctx.cfg = (int(norms), float(eps))
+        return ops.ucn_embedding_tail(a, b, size, norms=norms, eps=eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[0], b is not None and ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return None, None, None, None, None
+        norms, eps = ctx.cfg
+        gin = ops.ucn_embedding_tail_bwd(a, b, g.contiguous(), norms=norms, eps=eps)     # y.sum().backward() hands over stride 0
+        return (gin if need_a else None), (gin if need_b else None), None, None, None
+
+
+def ucn_embedding_tail(a, b, size, norms=1, eps=1e-12, fused=True):
+    """Differentiable tail of the UCN backbone: a, b (B, 64, h, w) fp32 low-resolution maps of the two towers in any memory format
+    (b None: one tower) -> (B, 64, H, W) = N(..N(upsample_bilinear(a) + upsample_bilinear(b))) for size = (H, W), N = F.normalize over
+    the channels applied ``norms`` (0..2) times.  fused: ops.ucn_embedding_tail forward and the msm_ucn_embedding_tail_bwd kernels
+    backward (one gradient tensor for both towers); ``fused=False`` or host tensors: the literal torch expression, which is the
+    definition."""
+    norms = int(norms)
+    if norms < 0 or norms > 2:
+        raise ValueError("ucn_embedding_tail: norms must be 0, 1 or 2")
+    size = (int(size[0]), int(size[1]))
+    if not fused or not a.is_cuda:
+        return _tail_torch(a, b, size, norms, eps)
+    return _UCNEmbeddingTail.apply(a, b, size, norms, eps)
+
+
+def _tower_forward_train(tower, x):
+    """Resnet34_8s up to its 1/8-resolution embedding (resnet_dilated.py:287-327 without the upsampling; resnet.py:43-73,248-258)
+    through the tower's own modules: nothing folded, every BatchNorm2d follows its own ``training`` flag."""
+    net = tower.resnet34_8s
+    x = F.max_pool2d(F.relu(net.bn1(net.conv1(x))), 3, stride=2, padding=1)
+    for i in range(4):
+        for blk in getattr(net, f"layer{i + 1}"):
+            y = F.relu(blk.bn1(blk.conv1(x)))
+            y = blk.bn2(blk.conv2(y))
+            x = F.relu(y + (x if blk.downsample is None else blk.downsample(x)))
+    return net.fc(x)
+
+
+def ucn_towers_forward_train(backbone, img, depth=None):
+    """The two towers of ``backbone`` (ucn_backbone.UCNBackbone) under autograd -> (lo_a, lo_b or None), the (B, num_units, h, w)
+    1/8-resolution maps the tail upsamples.  conv1 -> bn1 -> ReLU -> max-pool -> BasicBlocks -> fc through the modules themselves
+    (MIOpen convolutions and their autograd): a BatchNorm2d in training mode normalises with batch statistics and updates its running
+    statistics (the reference's ``network.train()``, lib/fcn/train.py:43), one in eval mode uses its running statistics.  One stream,
+    fp32; neither ``backbone.forward`` nor its folded-weight cache is touched."""
+    from ._plan import miopen_find
+    if backbone.backbone_dtype != "f32":
+        raise NotImplementedError("ucn_towers_forward_train: fp32 only (backbone_dtype is %r)" % (backbone.backbone_dtype,))
+    if depth is not None and backbone.fcn_depth is None:
+        raise RuntimeError("this backbone was built without a depth tower")
+    with miopen_find(bool(getattr(backbone, "miopen_find", True)) and img.is_cuda):
+        lo_a = _tower_forward_train(backbone.fcn, img.float())
+        lo_b = _tower_forward_train(backbone.fcn_depth, depth.float()) if depth is not None else None
+    return lo_a, lo_b
+
+
+def ucn_backbone_forward_train(backbone, img, depth=None, *, renormalize=False, fused_tail=True):
+    """``backbone(img, None, depth)`` under autograd -> (B, 64, H, W): ucn_towers_forward_train, then ucn_embedding_tail with
+    norms = backbone.normalize + renormalize (``renormalize``: the meta-arch's F.normalize of the backbone's output,
+    pretrained_meanshiftformer_model.py:298, inside the tail).  Works whatever ``backbone.training`` is: the BatchNorm modules decide
+    for themselves."""
+    lo_a, lo_b = ucn_towers_forward_train(backbone, img, depth)
+    if fused_tail and lo_a.is_cuda and lo_a.shape[1] != 64:
+        raise NotImplementedError("ucn_backbone_forward_train: the fused tail needs num_units == 64 (fused_tail=False runs torch's)")
+    norms = (1 if backbone.normalize else 0) + (1 if renormalize else 0)
+    return ucn_embedding_tail(lo_a, lo_b, img.shape[2:], norms=norms, fused=fused_tail)
+
+
+def ucn_model_losses(model, image, depth, targets, criterion, *, labels=None, embedding_loss=None, embedding_weight=None):
+    """The training branch of the RGB-D meta-arch from images (pretrained_meanshiftformer_model.py:283-333) for ``model`` =
+    meta_arch.PretrainedMeanShiftMaskFormer: image (B, 3, H, W) and depth (B, 3, H, W) xyz (None: colour only), normalised and padded
+    as ``model`` takes them -> the weighted loss dict.  The backbone runs under autograd (ucn_backbone_forward_train) with the
+    meta-arch's F.normalize (:298) as the tail's second normalisation, the rest is head_losses after its normalisation: the
+    embedding loss sees the same normalised tensor (:318 normalises a unit vector again).  Gradients reach every parameter of the
+    backbone and of the head."""
+    if embedding_loss is not None and (labels is None or embedding_weight is None):
+        raise ValueError("ucn_model_losses: embedding_loss needs labels and embedding_weight")
+    norm = ucn_backbone_forward_train(model.backbone, image, depth if model.use_depth else None, renormalize=True)
+    return _head_losses_normalised(model.sem_seg_head, norm, targets, criterion, labels, embedding_loss, embedding_weight)
