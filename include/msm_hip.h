@@ -53,6 +53,10 @@
  *                                   ros/test_images_segmentation_transformer.py:159-173, compute_xyz lib/fcn/get_backbone.py:96-102
  *   msm_prepare_inputs           <- (x - pixel_mean) / pixel_std, MSMFormer/meanshiftformer/meanshiftformer_model.py:241-242, and the
  *                                   zero padding of ImageList.from_tensors behind it
+ *   msm_target_* / msm_sample_labels
+ *                                <- TableTopDataset.__getitem__ lib/datasets/tabletop_dataset.py:319-407 (process_label_to_annos,
+ *                                   process_label, sample_pixels), TabletopDatasetMapper lib/datasets/tablet_instance_mapper.py:140-175,
+ *                                   prepare_targets MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:380-395
  *   msm_optim_*                  <- Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191: clip_grad_norm_ over
  *                                   the whole model, then torch.optim.AdamW with one param group per tensor
  */
@@ -71,7 +75,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 38   /* 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 39   /* 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1156,9 +1160,12 @@ int msm_eval_counts(const float* pred, const float* gt, int32_t* counts, void* w
  * through the four bilinear weights of every point (sigma and y recomputed at the saved points).
  *   table        device int64 [2 n_pred]: pred_masks base pointers, then the gradient base pointers ([B][Q][Hm][Wm] each,
  *                zero-initialised by the caller; only matched masks are written)
- *   flags        MSM_POINT_LOSS_GLOBAL_ATOMICS: scatter with global float atomics even where the mask fits in LDS
- *                (Hm Wm 4 <= 128 KiB: one workgroup accumulates its mask in LDS and writes it out whole).  The float atomics
- *                make the gradient's last bits depend on arrival order.
+ *   flags        MSM_POINT_LOSS_GLOBAL_ATOMICS: scatter with global float atomics even where the mask fits in LDS.
+ *   Where the mask fits in LDS one workgroup accumulates it there and writes it out whole: for (Hm Wm + 1) 8 <= 160 KiB (masks
+ *   up to 20 479 pixels, 120 x 160 among them) in 64-bit fixed point with integer atomics -- every contribution times a power of
+ *   two chosen per pair from a bound of the sum, rounded once, so the sum is independent of arrival order and the gradient
+ *   REPEATS BIT FOR BIT (a non-finite contribution makes that mask's whole gradient nan); for Hm Wm 4 <= 128 KiB as floats.
+ *   Float atomics (that form and the global one) make the gradient's last bits depend on arrival order.
  *
  * msm_lsap_match: the rectangular linear sum assignment of every (prediction, image) cost matrix of msm_match_cost, solved on
  * the device by shortest augmenting paths (Crouse 2016, the algorithm of scipy's linear_sum_assignment) in float64 on the
@@ -1267,6 +1274,70 @@ int msm_optim_grad_norm(const int64_t* tensors, const int64_t* chunks, double* p
 int msm_optim_adamw_step(const int64_t* tensors, const int64_t* chunks, const double* hyper, const double* partials,
                          int64_t* state, int n_tensors, int n_chunks, int n_rows, float max_norm, void* stream);
 int msm_optim_zero(const int64_t* tensors, const int64_t* chunks, int n_tensors, int n_chunks, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training targets from instance label images: what the reference builds per image on the host and uploads as T dense masks
+ * (TableTopDataset.__getitem__ lib/datasets/tabletop_dataset.py:319-407, TabletopDatasetMapper
+ * lib/datasets/tablet_instance_mapper.py:140-175, prepare_targets and the ImageList padding of the label map
+ * MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:319-321,380-395), for a batch, from the label images themselves.
+ * Definitions, per image b of raw [B][H][W] (uint8, or int32 with raw_is_i32), ids in [0, MSM_TARGET_BINS):
+ *   lab      = 0 where raw is one of background_ids, else raw (tabletop_dataset.py:335 folds the table, id 1)
+ *   present  = the distinct values of lab in ascending order (K_b of them); dense index of a value = its position in present
+ *   instances = present without a leading 0 (T_b of them, ascending id): mask lab == id, area, tight inclusive box.  An image
+ *              without any background pixel keeps its lowest id as dense index 0 AND as instance 0 (process_label and
+ *              process_label_to_annos do the same).
+ * All values are integers; every result is independent of the order in which pixels are visited.
+ *
+ * msm_target_tables: one launch, one workgroup per image, raw read once.
+ *   background_ids [n_background] int32 (device), 0 <= n_background <= 16; NULL with 0
+ *   tables   [B][MSM_TARGET_TABLE_ROW] int32 (msm_target_table_row() returns the row length), per image:
+ *              [0] pixels outside [0, MSM_TARGET_BINS) (int32 input; they belong to no value: callers raise)
+ *              [1] T_b   [2] K_b   [3] status bits of msm_target_write (written as 0 here)
+ *              [4 ..)    dense[MSM_TARGET_BINS]: raw id -> dense index (a background id maps where 0 maps), -1 absent
+ *              then      slot[MSM_TARGET_BINS]:  raw id -> instance row t in [0, T_b), -1 for background / absent ids
+ *              then      inst[MSM_TARGET_BINS - 1][6]: id, area, x_min, y_min, x_max, y_max of instance t; zero from T_b on
+ *
+ * msm_target_write: one launch; reads raw and tables, writes every byte of label_out and masks (torch.empty buffers are fine).
+ *   toff     [B + 1] int64 (device): image b writes mask rows toff[b] .. toff[b + 1] of the batch, as msm_match_cost reads them
+ *   label_out [B][Hp][Wp] float32 (label_is_f32; what msm_embloss_fwd reads) or int32: the dense index, 0 at the right / bottom
+ *              padding (ImageList.from_tensors pads the label map with 0) and where raw is outside [0, MSM_TARGET_BINS)
+ *   masks    [TT][Hp][Wp] uint8 0 / 1, zero in the padding: the `tgt` operand of msm_match_cost / msm_point_loss_*.  NULL: only
+ *              the label map is written (toff, boxes, ids, areas are not touched)
+ *   boxes    [TT][4] float32 x_min, y_min, x_max, y_max; ids [TT] int32; areas [TT] int32 -- the instance records in mask-row order
+ *   The rows an image writes are ITS toff range clamped into [0, TT] (at most MSM_TARGET_BINS of them), whatever the device
+ *   counts are: rows beyond T_b are written as zero (masks, boxes, ids, areas), instances beyond the range are dropped, and
+ *   bit 0 (MSM_TARGET_COUNT_MISMATCH) of tables[b][3] is set when toff[b + 1] - toff[b] != T_b.  Nothing outside rows [0, TT)
+ *   is ever written.  One lane per 16-pixel segment of a padded row: the ids are looked up once and the segment of every mask
+ *   row of the image is stored from them, 16 bytes per store where Wp % 16 == 0 and the outputs are 16-byte aligned (loads:
+ *   W % 16 == 0 and an aligned raw), element-wise otherwise: the same values either way.
+ *   B <= 65535, H W <= 2^24, Hp >= H, Wp >= W, Hp Wp <= 2^26.
+ *
+ * msm_sample_labels: sample_pixels (tabletop_dataset.py:303-316) as an exact, reproducible selection, in place on a label map.
+ *   labels   [B][Hp][Wp] float32 (label_is_f32) or int32; the valid H x W corner is sampled, the padding is not touched
+ *   keys     [B][H][W] int32, drawn by the caller (independent uniform keys make every subset equally likely, as the
+ *              reference's permutation(n)[:num] does)
+ *   For every image and every label i in [0, MSM_SAMPLE_MAX_LABELS) with n pixels: n <= num keeps them all; otherwise the num
+ *   pixels smallest in the order (key as a signed number, then flat index y W + x) keep their label and the others become -1.
+ *   Negative labels are left alone.  status [B] int32 = pixels whose label is not an integer below MSM_SAMPLE_MAX_LABELS
+ *   (left alone too; callers raise).
+ *   A radix select over the composite (key, index), 8 bits per step from the top: a clear and a count launch (pixels per
+ *   label), then per step one histogram launch (integer counters in LDS and global memory) and one scan launch (a wave per
+ *   label), ceil((32 + ceil(log2(H W))) / 8) <= 7 steps, then one launch that applies the thresholds; a label whose chosen
+ *   bin is taken whole is finished early and costs the later launches nothing.  No sort, no host round trip.  num >= 1.
+ *   workspace msm_sample_labels_workspace(B) bytes (device, 16-byte aligned); too small returns MSM_E_WORKSPACE. */
+#define MSM_TARGET_BINS 1024
+#define MSM_TARGET_TABLE_ROW 8190
+#define MSM_TARGET_COUNT_MISMATCH 1
+#define MSM_SAMPLE_MAX_LABELS 256
+int msm_target_table_row(void);
+int msm_target_tables(const void* raw, int raw_is_i32, const int32_t* background_ids, int n_background, int32_t* tables,
+                      int B, int H, int W, void* stream);
+int msm_target_write(const void* raw, int raw_is_i32, int32_t* tables, const int64_t* toff, void* label_out, int label_is_f32,
+                     uint8_t* masks, float* boxes, int32_t* ids, int32_t* areas, int B, int H, int W, int Hp, int Wp,
+                     int64_t TT, void* stream);
+int64_t msm_sample_labels_workspace(int B);
+int msm_sample_labels(void* labels, int label_is_f32, const int32_t* keys, int32_t* status, void* workspace,
+                      int64_t workspace_bytes, int B, int H, int W, int Hp, int Wp, int num, void* stream);
 
 #ifdef __cplusplus
 }

@@ -177,6 +177,23 @@ class _Batch:
         self.labels32 = self.labels.to(torch.int32)
 
 
+def _as_batch(targets, device, B):
+    """The targets of one call as the kernels read them: a targets.TargetBatch is used as it is (its concatenated uint8 masks,
+    labels and offsets: no torch.cat, no conversion), the reference's list goes through _Batch."""
+    if not getattr(targets, "is_target_batch", False):
+        return _Batch(targets, device)
+    if len(targets.T) != B:
+        raise RuntimeError(f"SetCriterion: a TargetBatch of {len(targets.T)} images for predictions of {B}")
+    m = targets.masks
+    if m.dtype != torch.uint8 or m.dim() != 3 or m.shape[0] != targets.toff[-1] or not m.is_contiguous():
+        raise RuntimeError(f"SetCriterion: TargetBatch.masks must be contiguous ({targets.toff[-1]}, Hg, Wg) uint8, got "
+                           f"{tuple(m.shape)} {m.dtype}")
+    if m.device != torch.device(device) or targets.labels32.device != m.device:
+        raise RuntimeError(f"SetCriterion: the TargetBatch lives on {m.device}, the predictions on {device}: build it from device "
+                           "label images (there is no copy behind the caller's back)")
+    return targets
+
+
 def _rand_into(out, generator):
     """torch.rand(out.shape) from `generator` (None: the default generator of out's device) into out, as one draw."""
     if generator is None or generator.device == out.device:
@@ -256,7 +273,7 @@ class HungarianMatcher(nn.Module):
         self._check()
         dev = outputs["pred_masks"].device
         B, Q = outputs["pred_logits"].shape[:2]
-        batch = _Batch(targets, dev)
+        batch = _as_batch(targets, dev, B)
         pts = torch.empty((1, B, int(self.num_points), 2), device=dev, dtype=torch.float32)
         self.draw_points(pts[0])
         cost = self.costs([outputs], batch, pts)
@@ -304,7 +321,9 @@ class _PointLosses(torch.autograd.Function):
 class SetCriterion(nn.Module):
     """criterion.py:90-247: Hungarian matching, then the classification loss and the point-sampled sigmoid-CE and dice mask
     losses for the final prediction and every auxiliary one.  forward(outputs, targets) -> the reference's dict of
-    UNWEIGHTED losses (loss_ce, loss_mask, loss_dice, then the same with _i for aux_outputs[i]).
+    UNWEIGHTED losses (loss_ce, loss_mask, loss_dice, then the same with _i for aux_outputs[i]).  ``targets`` is the reference's
+    list of {"labels", "masks"} or a targets.TargetBatch; the latter is read in place (its concatenated uint8 masks, int32 labels
+    and offsets: no torch.cat, no conversion), here and in HungarianMatcher.forward.
 
     After a call, ``last_indices`` holds the assignments per prediction, ``last_points`` the draws (draw_points) and
     ``last_selection`` the importance-sampling selection bitmaps (n_pred * N, ceil(Pos / 32)) int32 (bit i % 32 of word
@@ -396,7 +415,7 @@ class SetCriterion(nn.Module):
         logits0 = preds[0]["pred_logits"]
         dev = preds[0]["pred_masks"].device
         B, Q = logits0.shape[:2]
-        batch = _Batch(targets, dev)
+        batch = _as_batch(targets, dev, B)
         N = sum(min(Q, t) for t in batch.T)
         mp, os_, rnd = self.draw_points(n_pred, B, N, dev)
         self.last_points = (mp, os_, rnd)

@@ -15,7 +15,8 @@
 //                           list the backward reads) and the per-mask terms.
 //   point_loss_sum_kernel   one wave per prediction sums its per-mask terms in a fixed order (bit-reproducible losses).
 //   point_loss_bwd_kernel   one workgroup per matched mask: dL/dx per point, scattered through the four bilinear weights into
-//                           an LDS copy of the mask (written out whole) or, for large masks, by global float atomics.
+//                           an LDS copy of the mask (written out whole): 64-bit fixed point and integer atomics where the mask
+//                           fits (bit-reproducible gradients), floats above that, or, for large masks, global float atomics.
 #include "common.h"
 
 namespace {
@@ -24,7 +25,8 @@ using namespace msm;
 
 constexpr int CR_THREADS = 256;
 constexpr int CR_WAVES = CR_THREADS / 64;
-constexpr int64_t CR_LDS_MAX = 128 * 1024;     // bytes of one mask's gradient accumulated in LDS
+constexpr int64_t CR_LDS_MAX = 128 * 1024;     // bytes of one mask's gradient accumulated in LDS as floats
+constexpr int64_t CR_LDS_FIX_MAX = 160 * 1024; // ... and as 64-bit fixed point (the whole LDS of a CU: one workgroup on it)
 
 // grid_sample's source coordinate for align_corners=False, from the point_sample grid 2c - 1 (clamped so that a stray value
 // can never produce an out-of-range tap index; every in-range value is unchanged)
@@ -306,16 +308,26 @@ __global__ __launch_bounds__(64) void point_loss_sum_kernel(const float4* __rest
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // (c) backward.  table: [n_pred] mask pointers, [n_pred] gradient pointers (zero-initialised by the caller).
-// USE_LDS selects the scatter target at compile time: a pointer that may be either LDS or global memory would be a flat
-// pointer, and flat float atomics do not reach LDS.
-template <bool USE_LDS>
+// MODE selects the scatter target at compile time (a pointer that may be either LDS or global memory would be a flat pointer, and
+// flat float atomics do not reach LDS):
+//   CR_BWD_GLOBAL   float atomics on the gradient in global memory
+//   CR_BWD_LDS_F32  the mask's gradient as floats in LDS (float atomics), written out whole
+//   CR_BWD_LDS_FIX  the same as 64-bit fixed point: every contribution is scaled by a power of two S chosen per pair from a bound
+//                   of the sum (|contribution| <= dmax, at most one per point and pixel, so |sum| <= P dmax < 2^61 / S), rounded
+//                   once to an integer and added with INTEGER atomics, so the sum does not depend on arrival order and the
+//                   gradient repeats bit for bit; the quantum is 2^-61 of the bound, far below an fp32 ulp of any term that
+//                   matters.  A non-finite contribution (nan logits or gradients) makes the whole mask's gradient nan.
+enum { CR_BWD_GLOBAL = 0, CR_BWD_LDS_F32 = 1, CR_BWD_LDS_FIX = 2 };
+
+template <int MODE>
 __global__ __launch_bounds__(CR_THREADS) void point_loss_bwd_kernel(const int64_t* __restrict__ table, const uint8_t* __restrict__ tgt,
                                                                     const int32_t* __restrict__ pairs, const float* __restrict__ os_pts,
                                                                     const float* __restrict__ rnd_pts, const float4* __restrict__ terms,
                                                                     const int32_t* __restrict__ sel_idx, const float* __restrict__ gl,
                                                                     int n_pred, int N, int BQ, int TT, int Hm, int Wm, int Hg, int Wg,
                                                                     int Pos, int k, int P, float num_masks) {
-    extern __shared__ __attribute__((aligned(16))) float acc[];       // [Hm * Wm] when USE_LDS
+    extern __shared__ __attribute__((aligned(16))) float acc[];       // LDS_F32: [Hm * Wm] floats; LDS_FIX: [Hm * Wm + 1] 64-bit words
+    unsigned long long* acc64 = reinterpret_cast<unsigned long long*>(acc);
     const int pair = blockIdx.x, tid = threadIdx.x;
     const PairView pv = cr_pair(pairs, pair, n_pred, N, BQ, TT);
     if (!pv.ok) return;
@@ -331,14 +343,33 @@ __global__ __launch_bounds__(CR_THREADS) void point_loss_bwd_kernel(const int64_
     const float g_ce = gl[pv.pred] / ((float)P * num_masks);
     const float g_d = gl[n_pred + pv.pred] / num_masks;
     const float dnum = 2.f * a + 1.f, dden = bp1 * bp1;
-    if (USE_LDS) {
+    double scale = 0.0;                                   // LDS_FIX: the power of two S (0: the bound itself is not finite)
+    if (MODE == CR_BWD_LDS_FIX) {
+        // |d| <= |g_ce| |s - y| + |g_d| |2 y bp1 - dnum| / dden s (1 - s) with |s - y| <= 1, y in [0, 1], s (1 - s) <= 1 / 4
+        const double dmax = fabs((double)g_ce) + fabs((double)g_d) * (2.0 * fabs((double)bp1) + fabs((double)dnum)) / (double)dden * 0.25;
+        const double bound = (double)P * dmax;
+        if (bound > 0.0 && bound < 1.0e300) {
+            int e;
+            frexp(bound, &e);                             // bound < 2^e
+            scale = ldexp(1.0, 61 - e);
+        }
+        for (int i = tid; i <= HW; i += CR_THREADS) acc64[i] = 0ull;          // [HW]: the non-finite flag
+        __syncthreads();
+    }
+    if (MODE == CR_BWD_LDS_F32) {
         for (int i = tid; i < HW; i += CR_THREADS) acc[i] = 0.f;
         __syncthreads();
     }
     auto add = [&](int i, float v) {
-        if (USE_LDS) atomicAdd(acc + i, v);
-        else __hip_atomic_fetch_add(((__attribute__((address_space(1))) float*)g) + i, v, __ATOMIC_RELAXED,
-                                    __HIP_MEMORY_SCOPE_AGENT);
+        if (MODE == CR_BWD_LDS_FIX) {
+            const double q = (double)v * scale;
+            if (fabs(q) < 4.0e18) atomicAdd(acc64 + i, (unsigned long long)__double2ll_rn(q));
+            else atomicOr(acc64 + HW, 1ull);              // nan, inf or beyond the bound (a non-finite bound: scale = 0 and q = nan or 0)
+        } else if (MODE == CR_BWD_LDS_F32) {
+            atomicAdd(acc + i, v);
+        } else {
+            __hip_atomic_fetch_add(((__attribute__((address_space(1))) float*)g) + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     };
     for (int j = tid; j < P; j += CR_THREADS) {
         float cx, cy;
@@ -365,7 +396,14 @@ __global__ __launch_bounds__(CR_THREADS) void point_loss_bwd_kernel(const int64_
             if (xb) add((y0 + 1) * Wm + x0 + 1, e * so * d);
         }
     }
-    if (USE_LDS) {
+    if (MODE == CR_BWD_LDS_FIX) {
+        __syncthreads();
+        const bool poisoned = acc64[HW] != 0ull || scale == 0.0 && (g_ce != 0.f || g_d != 0.f);
+        const double inv = scale > 0.0 ? 1.0 / scale : 0.0;                   // a power of two: exact
+        for (int i = tid; i < HW; i += CR_THREADS)
+            g[i] = poisoned ? __int_as_float(0x7fc00000) : (float)((double)(long long)acc64[i] * inv);
+    }
+    if (MODE == CR_BWD_LDS_F32) {
         __syncthreads();
         for (int i = tid; i < HW; i += CR_THREADS) g[i] = acc[i];
     }
@@ -444,17 +482,22 @@ extern "C" int msm_point_loss_bwd(const int64_t* table, const uint8_t* tgt, cons
     MSM_REQUIRE(tgt && pairs && os_points && rnd_points && workspace, "msm_point_loss_bwd: null pointer");
     const float4* terms = static_cast<const float4*>(workspace);
     const int32_t* idx = reinterpret_cast<const int32_t*>(terms + n_pairs);
-    const int64_t lds_bytes = (int64_t)Hm * Wm * 4;
-    const bool use_lds = (flags & MSM_POINT_LOSS_GLOBAL_ATOMICS) == 0 && lds_bytes <= CR_LDS_MAX;
+    const int64_t fix_bytes = ((int64_t)Hm * Wm + 1) * 8, f32_bytes = (int64_t)Hm * Wm * 4;
+    const bool lds = (flags & MSM_POINT_LOSS_GLOBAL_ATOMICS) == 0;
     hipStream_t s = (hipStream_t)stream;
-    if (use_lds) {
-        MSM_CHECK_HIP((hipError_t)msm::ensure_dynamic_lds((const void*)point_loss_bwd_kernel<true>, (size_t)lds_bytes));
-        hipLaunchKernelGGL(point_loss_bwd_kernel<true>, dim3((unsigned)n_pairs), dim3(CR_THREADS), (size_t)lds_bytes, s, table, tgt,
-                           pairs, os_points, rnd_points, terms, idx, grad_losses, n_pred, N, BQ, TT, Hm, Wm, Hg, Wg, Pos, k, P, num_masks);
+#define MSM_PL_BWD(MODE, BYTES)                                                                                                     \
+    hipLaunchKernelGGL(point_loss_bwd_kernel<MODE>, dim3((unsigned)n_pairs), dim3(CR_THREADS), (size_t)(BYTES), s, table, tgt, pairs, \
+                       os_points, rnd_points, terms, idx, grad_losses, n_pred, N, BQ, TT, Hm, Wm, Hg, Wg, Pos, k, P, num_masks)
+    if (lds && fix_bytes <= CR_LDS_FIX_MAX) {              // reproducible: masks up to 20 479 pixels (120 x 160 among them)
+        MSM_CHECK_HIP((hipError_t)msm::ensure_dynamic_lds((const void*)point_loss_bwd_kernel<CR_BWD_LDS_FIX>, (size_t)fix_bytes));
+        MSM_PL_BWD(CR_BWD_LDS_FIX, fix_bytes);
+    } else if (lds && f32_bytes <= CR_LDS_MAX) {
+        MSM_CHECK_HIP((hipError_t)msm::ensure_dynamic_lds((const void*)point_loss_bwd_kernel<CR_BWD_LDS_F32>, (size_t)f32_bytes));
+        MSM_PL_BWD(CR_BWD_LDS_F32, f32_bytes);
     } else {
-        hipLaunchKernelGGL(point_loss_bwd_kernel<false>, dim3((unsigned)n_pairs), dim3(CR_THREADS), 0, s, table, tgt, pairs, os_points,
-                           rnd_points, terms, idx, grad_losses, n_pred, N, BQ, TT, Hm, Wm, Hg, Wg, Pos, k, P, num_masks);
+        MSM_PL_BWD(CR_BWD_GLOBAL, 0);
     }
+#undef MSM_PL_BWD
     MSM_CHECK_LAUNCH("msm_point_loss_bwd");
     return MSM_OK;
 }

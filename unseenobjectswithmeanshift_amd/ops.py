@@ -2018,6 +2018,105 @@ def prepare_inputs(image, depth=None, *, mean=None, std=None, frame=None, out_im
     return image_out, depth_out
 
 
+# ---- training targets from instance label images (targets.py; csrc/targets.hip) ----
+TARGET_BINS = 1024           # MSM_TARGET_BINS: instance ids lie in [0, 1024)
+SAMPLE_MAX_LABELS = 256      # MSM_SAMPLE_MAX_LABELS: dense labels per image msm_sample_labels selects for
+TARGET_COUNT_MISMATCH = 1    # MSM_TARGET_COUNT_MISMATCH: bit of tables[b][3]
+_RAW_DTYPES = (torch.uint8, torch.int32)
+_LABEL_DTYPES = (torch.float32, torch.int32)
+
+
+def _check_raw(raw, who):
+    if raw.dtype not in _RAW_DTYPES:
+        raise RuntimeError(f"{who}: raw must be uint8 or int32, got {raw.dtype}")
+    _c(raw, "raw", raw.dtype)
+    if raw.dim() != 3 or 0 in raw.shape:
+        raise RuntimeError(f"{who}: raw {tuple(raw.shape)} must be a non-empty (B, H, W)")
+
+
+def target_tables(raw, background_ids=None):
+    """The per-image tables of a batch of instance label images in one launch (msm_target_tables): raw (B,H,W) uint8 or int32
+    with ids in [0, 1024), background_ids: int32 device tensor of the ids folded to 0 (None: none) -> tables (B, row) int32
+    laid out as include/msm_hip.h documents: [0] out-of-range pixels, [1] T_b, [2] K_b, [3] status bits of target_write, the
+    id -> dense index and id -> mask row tables, the instance records (id, area, x_min, y_min, x_max, y_max)."""
+    _check_raw(raw, "target_tables")
+    _c(background_ids, "background_ids", torch.int32)
+    B, H, W = raw.shape
+    tables = torch.empty((B, lib().msm_target_table_row()), device=raw.device, dtype=torch.int32)
+    n_bg = 0 if background_ids is None else background_ids.numel()
+    check(lib().msm_target_tables(_p(raw), 1 if raw.dtype == torch.int32 else 0, _p(background_ids if n_bg else None), n_bg,
+                                  _p(tables), B, H, W, _stream()), "msm_target_tables")
+    return tables
+
+
+def target_write(raw, tables, toff=None, total=0, *, frame=None, label_dtype=torch.float32, masks=None):
+    """The padded dense label map and, with ``toff``, the (TT,Hp,Wp) uint8 masks of a batch in one launch (msm_target_write):
+    raw and tables as target_tables took / returned them, toff: (B+1,) int64 DEVICE tensor of mask-row offsets and ``total`` =
+    TT rows in the buffer (the launch never writes another row: a count that disagrees with the device's sets bit 0 of
+    tables[b][3]), frame = (Hp, Wp) (default (H, W)) -> (label (B,Hp,Wp) of ``label_dtype`` float32 / int32, masks or None,
+    boxes (TT,4) float32, ids (TT,) int32, areas (TT,) int32).  ``masks``: a (TT,Hp,Wp) uint8 buffer to write into."""
+    _check_raw(raw, "target_write")
+    _c(tables, "tables", torch.int32), _c(toff, "toff", torch.int64)
+    B, H, W = raw.shape
+    dev = raw.device
+    Hp, Wp = (H, W) if frame is None else (int(frame[0]), int(frame[1]))
+    if tuple(tables.shape) != (B, lib().msm_target_table_row()) or tables.device != dev:
+        raise RuntimeError(f"target_write: tables {tuple(tables.shape)} on {tables.device} do not belong to {B} images on {dev}")
+    if label_dtype not in _LABEL_DTYPES:
+        raise RuntimeError(f"target_write: label_dtype must be float32 or int32, got {label_dtype}")
+    label = torch.empty((B, Hp, Wp), device=dev, dtype=label_dtype)
+    boxes = ids = areas = None
+    TT = int(total)
+    if toff is None:
+        if masks is not None or TT:
+            raise RuntimeError("target_write: masks need toff")
+    else:
+        if tuple(toff.shape) != (B + 1,) or toff.device != dev or TT < 0:
+            raise RuntimeError(f"target_write: toff {tuple(toff.shape)} on {toff.device} must be ({B + 1},) on {dev}")
+        if masks is None:
+            masks = torch.empty((TT, Hp, Wp), device=dev, dtype=torch.uint8)
+        _c(masks, "masks", torch.uint8)
+        if tuple(masks.shape) != (TT, Hp, Wp) or masks.device != dev:
+            raise RuntimeError(f"target_write: masks {tuple(masks.shape)} on {masks.device} must be {(TT, Hp, Wp)} on {dev}")
+        boxes = torch.empty((TT, 4), device=dev, dtype=torch.float32)
+        ids = torch.empty((TT,), device=dev, dtype=torch.int32)
+        areas = torch.empty((TT,), device=dev, dtype=torch.int32)
+    # an empty mask buffer has no address: the kernel still takes the toff path (status, nothing to write) through a dummy
+    mp = masks if masks is None or TT else torch.empty((1,), device=dev, dtype=torch.uint8)
+    check(lib().msm_target_write(_p(raw), 1 if raw.dtype == torch.int32 else 0, _p(tables), _p(toff), _p(label),
+                                 1 if label_dtype == torch.float32 else 0, _p(mp), _p(boxes if TT else mp), _p(ids if TT else mp),
+                                 _p(areas if TT else mp), B, H, W, Hp, Wp, TT, _stream()), "msm_target_write")
+    return label, masks, boxes, ids, areas
+
+
+def sample_labels_(label, keys, num, image_size=None):
+    """sample_pixels in place (msm_sample_labels): label (B,Hp,Wp) float32 or int32 dense labels, keys (B,H,W) int32, (H, W) =
+    ``image_size`` (default: the whole map) the corner that is sampled.  Per image and label in [0, 256) with more than
+    ``num`` pixels, the ``num`` smallest by (key, flat index) stay and the others become -1.  Returns status (B,) int32: pixels
+    whose label is not an integer below 256 (for the caller to read when it chooses to; nothing here waits)."""
+    if label.dtype not in _LABEL_DTYPES:
+        raise RuntimeError(f"sample_labels_: label must be float32 or int32, got {label.dtype}")
+    _c(label, "label", label.dtype), _c(keys, "keys", torch.int32)
+    if label.dim() != 3 or 0 in label.shape:
+        raise RuntimeError(f"sample_labels_: label {tuple(label.shape)} must be a non-empty (B, Hp, Wp)")
+    B, Hp, Wp = label.shape
+    H, W = (Hp, Wp) if image_size is None else (int(image_size[0]), int(image_size[1]))
+    if tuple(keys.shape) != (B, H, W) or keys.device != label.device or not (0 < H <= Hp and 0 < W <= Wp):
+        raise RuntimeError(f"sample_labels_: keys {tuple(keys.shape)} on {keys.device} must be {(B, H, W)} on {label.device}, "
+                           f"inside the {Hp}x{Wp} map")
+    if int(num) < 1:
+        raise ValueError(f"sample_labels_: num must be at least 1, got {num}")
+    dev = label.device
+    nbytes = lib().msm_sample_labels_workspace(B)
+    if nbytes < 0:
+        check(int(nbytes), "msm_sample_labels_workspace")
+    ws = torch.empty((nbytes // 4,), device=dev, dtype=torch.int32)
+    status = torch.empty((B,), device=dev, dtype=torch.int32)
+    check(lib().msm_sample_labels(_p(label), 1 if label.dtype == torch.float32 else 0, _p(keys), _p(status), _p(ws), nbytes, B, H, W,
+                                  Hp, Wp, int(num), _stream()), "msm_sample_labels")
+    return status
+
+
 # ----------------------------------------------------------------------------------------------
 # backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------
