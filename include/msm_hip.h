@@ -75,7 +75,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 39   /* 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 40   /* 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -340,6 +340,29 @@ int msm_msdeform_attn_bwd(const float* value, const int64_t* spatial_shapes,
                           const float* attn_weight, const float* grad_output,
                           float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
                           int B, int S, int M, int D, int L, int Lq, int P, void* stream);
+/* The same backward with results that are a pure function of the call's inputs (csrc/msda_det.hip, DESIGN.md 5x): float32,
+ * D <= 64 and L <= 8 only (anything else returns MSM_E_INVALID with a message; there is no fall-back to the atomic kernels).
+ *   grad_value[b][s][m][c] is the exact integer sum of its contributions w_k * (go_c * a), each rounded once to a 64-bit fixed-point
+ *   grid whose step 2^-e is chosen per destination (b, s, m) from the largest contribution bound and the number of contributions
+ *   there; it does not depend on the grid, the arrival order, the order of queries or points, the other images or the workspace
+ *   size.  A destination that receives a non-finite contribution is NaN in all its D channels (a deviation from IEEE inf
+ *   arithmetic); no other destination changes.  grad_sampling_loc / grad_attn_weight: a fixed-order reduction over the head's
+ *   lanes, no atomics; msm_msdeform_attn_bwd's arithmetic when D/4 (D when D % 4 != 0) is a power of two.
+ *   workspace  msm_msdeform_attn_bwd_det_workspace(B, S, M, D) = B * S * M * 8 * (D + 1) bytes for the whole batch, 16-byte aligned,
+ *              contents ignored and overwritten: per image a table [S][M] of {uint32 bits of the largest bound, uint32 count}
+ *              followed by int64 accumulators [S][M][D].  With fewer bytes, but at least one image's (B = 1), the images run in
+ *              groups of workspace_bytes / one image's bytes, same bits; below one image: MSM_E_INVALID.  Bytes past
+ *              (images per group) * (one image's bytes) are not touched.
+ *   Per group: four kernels on `stream` (the first zeroes the group's workspace; no hipMemsetAsync, so a captured graph holds
+ *   kernel nodes only); every element of the three outputs is written (no zero-fill of the outputs).  value, grad_output,
+ *   grad_value 16-byte aligned. */
+int64_t msm_msdeform_attn_bwd_det_workspace(int B, int S, int M, int D);
+int msm_msdeform_attn_bwd_det(const float* value, const int64_t* spatial_shapes,
+                              const int64_t* level_start_index, const float* sampling_loc,
+                              const float* attn_weight, const float* grad_output,
+                              float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                              int B, int S, int M, int D, int L, int Lq, int P,
+                              void* workspace, int64_t workspace_bytes, void* stream);
 int msm_msdeform_attn_fwd_f64(const double* value, const int64_t* spatial_shapes,
                               const int64_t* level_start_index, const double* sampling_loc,
                               const double* attn_weight, double* out,

@@ -6,6 +6,7 @@ on torch's current stream.  Tensors must be fp32 and live on a ROCm device; ther
 The weight layouts that need no launch (pack_encoder_block*, pack_conv_in_weight*, ...) are packing.py's, re-exported here.
 """
 import ctypes
+import warnings
 
 import torch
 
@@ -1122,8 +1123,43 @@ def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations,
     return out
 
 
-def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output):
-    """Reference-ABI backward: returns (grad_value, grad_sampling_loc, grad_attn_weight).  float32 or float64."""
+MSDA_DET_MAX_D, MSDA_DET_MAX_L = 64, 8     # the range of msm_msdeform_attn_bwd_det (float32)
+
+
+def msda_backward_deterministic(deterministic=None):
+    """The form ms_deform_attn_backward takes: ``deterministic`` itself, or torch's global flag when it is None."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+
+
+def ms_deform_attn_backward_det_workspace(N, S, M, D):
+    """Bytes of workspace the deterministic backward takes for N images (msm_msdeform_attn_bwd_det_workspace)."""
+    return int(lib().msm_msdeform_attn_bwd_det_workspace(int(N), int(S), int(M), int(D)))
+
+
+def _msda_det_supported(value, sampling_locations):
+    """False (after a warning) where the deterministic backward does not exist and torch's warn-only mode is on; raises otherwise."""
+    D, L = value.shape[3], sampling_locations.shape[3]
+    if value.dtype == torch.float32 and D <= MSDA_DET_MAX_D and L <= MSDA_DET_MAX_L:
+        return True
+    msg = (f"ms_deform_attn_backward does not have a deterministic implementation for dtype {value.dtype}, D={D}, L={L} "
+           f"(float32, D <= {MSDA_DET_MAX_D}, L <= {MSDA_DET_MAX_L} only), but a deterministic result was requested "
+           "(deterministic=True or torch.use_deterministic_algorithms(True))")
+    if torch.is_deterministic_algorithms_warn_only_enabled():
+        warnings.warn(msg + "; running the atomic kernel, whose last bits depend on scheduling", UserWarning, stacklevel=3)
+        return False
+    raise RuntimeError(msg + ". Pass deterministic=False, or torch.use_deterministic_algorithms(True, warn_only=True), to run the atomic kernel.")
+
+
+def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output,
+                            deterministic=None, workspace_images=None, workspace=None):
+    """Reference-ABI backward: returns (grad_value, grad_sampling_loc, grad_attn_weight).  float32 or float64.
+    deterministic: None follows torch.are_deterministic_algorithms_enabled(), True / False force the choice.  The deterministic form
+    (msm_msdeform_attn_bwd_det: float32, D <= 64, L <= 8) gives results that are a pure function of the inputs -- the same bits
+    on every call, under any order of queries or points and for any batch around an image; outside its range a request raises, or
+    warns and runs the atomic kernel under torch's warn_only mode.  Its workspace is allocated here for the whole batch, for
+    ``workspace_images`` images (the images then run in groups; same bits), or is the caller's ``workspace`` (a contiguous uint8
+    device tensor of at least one image's bytes, see ms_deform_attn_backward_det_workspace)."""
+    det = msda_backward_deterministic(deterministic) and _msda_det_supported(value, sampling_locations)
     dt = _msda_dtype(value, ((value, "value"), (sampling_locations, "sampling_locations"),
                              (attention_weights, "attention_weights"), (grad_output, "grad_output")))
     _c(spatial_shapes, "spatial_shapes", torch.int64), _c(level_start_index, "level_start_index", torch.int64)
@@ -1134,6 +1170,17 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     gv = torch.empty_like(value)
     gl = torch.empty_like(sampling_locations)
     gw = torch.empty_like(attention_weights)
+    if det:
+        if workspace is None:
+            images = N if workspace_images is None else max(1, min(N, int(workspace_images)))
+            workspace = torch.empty(ms_deform_attn_backward_det_workspace(images, S, M, D), device=value.device, dtype=torch.uint8)
+        else:
+            _c(workspace, "workspace", torch.uint8)
+        rc = lib().msm_msdeform_attn_bwd_det(_p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_locations),
+                                             _p(attention_weights), _p(grad_output), _p(gv), _p(gl), _p(gw),
+                                             N, S, M, D, L, Lq, P, _p(workspace), workspace.numel(), _stream())
+        check(rc, "msm_msdeform_attn_bwd_det")
+        return gv, gl, gw
     fn, what = ((lib().msm_msdeform_attn_bwd, "msm_msdeform_attn_bwd") if dt == torch.float32 else
                 (lib().msm_msdeform_attn_bwd_f64, "msm_msdeform_attn_bwd_f64"))
     rc = fn(_p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_locations),
