@@ -57,6 +57,9 @@
  *                                <- TableTopDataset.__getitem__ lib/datasets/tabletop_dataset.py:319-407 (process_label_to_annos,
  *                                   process_label, sample_pixels), TabletopDatasetMapper lib/datasets/tablet_instance_mapper.py:140-175,
  *                                   prepare_targets MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:380-395
+ *   msm_augment_* / msm_xyz_noise
+ *                                <- chromatic_transform / add_noise lib/utils/blob.py:74-129, add_noise_to_depth /
+ *                                   dropout_random_ellipses / add_noise_to_xyz lib/utils/augmentation.py:58-126
  *   msm_optim_*                  <- Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191: clip_grad_norm_ over
  *                                   the whole model, then torch.optim.AdamW with one param group per tensor
  */
@@ -75,7 +78,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 40   /* 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 41   /* 41: msm_augment_color / msm_augment_depth + msm_augment_depth_workspace / msm_xyz_noise, msm_augment_table_row (the training loader's random augmentations of a batch on the device: HLS shift, pixel noise, motion blur, depth scaling and ellipse dropout, point-cloud noise); 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1361,6 +1364,79 @@ int msm_target_write(const void* raw, int raw_is_i32, int32_t* tables, const int
 int64_t msm_sample_labels_workspace(int B);
 int msm_sample_labels(void* labels, int label_is_f32, const int32_t* keys, int32_t* status, void* workspace,
                       int64_t workspace_bytes, int B, int H, int W, int Hp, int Wp, int num, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Random augmentations of the training loader (TableTopDataset.__getitem__ lib/datasets/tabletop_dataset.py:161-181,364-367) for a
+ * batch of frames.  Every random number is drawn by the caller: the per-image scalars arrive in `table`, the two normal fields as
+ * tensors; the kernels are pure functions.  Every step below is fp32 (or an integer), round to nearest, in the written order:
+ * no multiply-add, no reciprocal.  The reference calls cv2 for all of this; the definitions are this library's own, the numpy
+ * host path of augment.py states them a second time, and the two agree bit for bit.
+ *
+ *   table  [B][MSM_AUGMENT_TABLE_ROW] int32 words (floats by their bits), per image:
+ *            [0] flags: MSM_AUGMENT_CHROMATIC | _GAUSSIAN | _BLUR (colour), _DEPTH (depth); _GAUSSIAN and _BLUR exclude each other
+ *            [1] blur size, one of 3 5 7 9 11 15   [2] 1: blur along x, 0: along y
+ *            [3] d_h  [4] d_l  [5] d_s  [6] sigma  [7] depth multiplier m   (float)
+ *            [8] ellipse count in [0, MSM_AUGMENT_ELLIPSE_MAX]
+ *            [16 + 5 i ..) ellipse i: rx, ry, cos, sin (float), key (uint32)
+ *   status [B][4] int32: word 0 is written by msm_augment_color, word 1 by msm_augment_depth; MSM_AUGMENT_BAD_* bits.  A row that
+ *          cannot be carried out (unknown flags or blur size, a blur wider than the image, a value that is not finite or out of
+ *          range, more than 32 ellipses) is SKIPPED -- the frame is copied / only converted -- and reported here; an ellipse with a
+ *          radius outside [0, 65536] or a (cos, sin) off the unit circle by more than 1e-3 is skipped alone.  Every index taken
+ *          from a table is bounded first: a wrong table never causes an access outside the buffers.
+ *
+ * msm_augment_color: color, out [B][H][W][3] uint8 BGR (out != color), noise [B][H][W] float or NULL (a _GAUSSIAN row then is a bad row).
+ *   D1 (_CHROMATIC), OpenCV's documented 8-bit BGR <-> HLS conversion:
+ *     b, g, r = float(v) / 255; sum = vmax + vmin; diff = vmax - vmin; l = sum * 0.5; diff <= FLT_EPSILON: h = s = 0, else
+ *     s = diff / sum (l < 0.5) or diff / ((2 - vmax) - vmin); k = 60 / diff; h = (g - b) k | (b - r) k + 120 | (r - g) k + 240 by
+ *     the channel that equals vmax (r first, then g); h < 0: h += 360; h = h * 0.5; H, L, S = rint(h), rint(l * 255), rint(s * 255)
+ *     H' = trunc(mod(H + d_h, 180)) (the result takes the divisor's sign; it can be exactly 180), L' = trunc(clip(L + d_l, 0, 255)),
+ *     S' likewise; |d_h| <= 180, |d_l|, |d_s| <= 512
+ *     l = L' / 255, s = S' / 255; s == 0: grey l, else p2 = l (1 + s) (l <= 0.5) or (l + s) - l s; p1 = 2 l - p2; d = p2 - p1;
+ *     h = (H' 6) / 180, h >= 6: h -= 6; sector = floor(h), f = h - sector; tab = p2, p1, p1 + d (1 - f), p1 + d f;
+ *     (b, g, r) = tab[{1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0}][sector]; out = clip(rint(x * 255), 0, 255)
+ *   D2 (_GAUSSIAN, after D1): out_c = trunc(clip(float(v_c) + sigma * noise[y][x], 0, 255)), the same noise for the three channels
+ *   D3 (_BLUR, after D1): a box of `size` taps along x or y, borders reflect-101, out = (2 sum + size) / (2 size) in integers;
+ *     the blurred extent must exceed size / 2
+ *   One launch; a 16 x 64 pixel tile per workgroup.  B <= 65535, B H W < 2^31.
+ *
+ * msm_augment_depth: depth [B][H][W] uint16 (depth_is_u16: z = float(d) / depth_div) or float (z = d, NaN -> 0), out [B][H][W] float.
+ *   D4 (_DEPTH; without the flag the map is only converted): z = z * m; the valid pixels are z > 0 in row-major order, n of them;
+ *     ellipse i has its centre (cx, cy) at valid pixel number (uint64(key_i) * n) >> 32 (n = 0: no dropout); a pixel becomes 0 if for
+ *     any ellipse  dx = x - cx, dy = y - cy, u = dx cos + dy sin, v = dy cos - dx sin, a = max(rx, 0.5), b = max(ry, 0.5),
+ *     (u u) / (a a) + (v v) / (b b) <= 1.
+ *   stages: bit 0 runs the launches (a1) -- valid pixels per row, over the whole chip -- and (a2) -- one workgroup per image: the scan
+ *     of the row counts, the centres -> one record block of MSM_AUGMENT_RECORD_ROW int32 words per image at the head of `workspace`
+ *     (msm_augment_depth_workspace bytes; the B H row counts follow the B blocks): [count, n, m, 0 x 5] then 32 x [cx, cy, x0, x1,
+ *     y0, y1, a a, b b, cos, sin, 0, 0], the box x0 > x1 marking an entry to skip, and status word 1; bit 1 runs launch (b) --
+ *     scale, test, store -- which ORs
+ *     MSM_AUGMENT_BAD_CENTRE into status word 1 for a record whose centre lies outside the image (and skips it).  3 is the product path.
+ *   B <= 65535, H <= MSM_AUGMENT_MAX_H, W <= 65536, B H W < 2^31, else MSM_E_INVALID (the workspace query too).
+ *
+ * msm_xyz_noise: D5, in place on xyz [B][3][Hp][Wp]: where xyz[2] > 0 inside the H x W corner, xyz[c] = xyz[c] + scale * up(gp[c]),
+ *   gp [B][3][h][w]; taps [H + W][8] int32 (the H rows' then the W columns' four source indices and four float weight bits, built by
+ *   the host: augment.bicubic_taps, a = -0.75, half-pixel centres, clamped); up = ((w0 v0 + w1 v1) + w2 v2) + w3 v3 along x for
+ *   the four rows, then the same along y.  One launch.  B Hp Wp < 2^30. */
+#define MSM_AUGMENT_TABLE_ROW 176
+#define MSM_AUGMENT_ELLIPSE_MAX 32
+#define MSM_AUGMENT_ELLIPSE_WORDS 5
+#define MSM_AUGMENT_MAX_H 8192
+#define MSM_AUGMENT_RECORD_ROW 392
+#define MSM_AUGMENT_CHROMATIC 1
+#define MSM_AUGMENT_GAUSSIAN 2
+#define MSM_AUGMENT_BLUR 4
+#define MSM_AUGMENT_DEPTH 8
+#define MSM_AUGMENT_BAD_ROW 1
+#define MSM_AUGMENT_BAD_COUNT 2
+#define MSM_AUGMENT_BAD_ELLIPSE 4
+#define MSM_AUGMENT_BAD_CENTRE 8
+int msm_augment_table_row(void);
+int msm_augment_color(const uint8_t* color, const int32_t* table, const float* noise, uint8_t* out, int32_t* status, int B, int H,
+                      int W, void* stream);
+int64_t msm_augment_depth_workspace(int B, int H, int W);
+int msm_augment_depth(const void* depth, int depth_is_u16, float depth_div, const int32_t* table, float* out, int32_t* status,
+                      void* workspace, int64_t workspace_bytes, int stages, int B, int H, int W, void* stream);
+int msm_xyz_noise(float* xyz, const float* gp, const int32_t* taps, float scale, int B, int H, int W, int Hp, int Wp, int h, int w,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -2164,6 +2164,87 @@ def sample_labels_(label, keys, num, image_size=None):
     return status
 
 
+# ---- random augmentations of the training loader (augment.py; csrc/augment.hip) ----
+AUGMENT_RECORD_ROW = 392     # MSM_AUGMENT_RECORD_ROW: int32 words of one image's ellipse records, B blocks at the head of the workspace
+
+
+def _check_augment_table(table, status, B, dev, who):
+    _c(table, "table", torch.int32), _c(status, "status", torch.int32)
+    if tuple(table.shape) != (B, lib().msm_augment_table_row()) or table.device != dev:
+        raise RuntimeError(f"{who}: table {tuple(table.shape)} on {table.device} must be ({B}, {lib().msm_augment_table_row()}) on {dev}")
+    if tuple(status.shape) != (B, 4) or status.device != dev:
+        raise RuntimeError(f"{who}: status {tuple(status.shape)} on {status.device} must be ({B}, 4) on {dev}")
+
+
+def augment_color(color, table, noise, status, *, out=None):
+    """D1-D3 of augment.py on a batch in one launch (msm_augment_color): color (B,H,W,3) uint8 BGR, table (B,176) int32
+    (augment.pack_table), noise (B,H,W) float32 or None, status (B,4) int32 whose column 0 the launch writes -> a new (B,H,W,3)
+    uint8 tensor (or ``out``, a contiguous tensor of that shape that is not ``color``).  Nothing here waits."""
+    _c(color, "color", torch.uint8), _c(noise, "noise")
+    if color.dim() != 4 or color.shape[-1] != 3 or 0 in color.shape:
+        raise RuntimeError(f"augment_color: color {tuple(color.shape)} must be a non-empty (B, H, W, 3)")
+    B, H, W, _ = color.shape
+    dev = color.device
+    _check_augment_table(table, status, B, dev, "augment_color")
+    if noise is not None and (tuple(noise.shape) != (B, H, W) or noise.device != dev):
+        raise RuntimeError(f"augment_color: noise {tuple(noise.shape)} on {noise.device} must be {(B, H, W)} on {dev}")
+    if out is None:
+        out = torch.empty_like(color)
+    _c(out, "out", torch.uint8)
+    if out.shape != color.shape or out.device != dev or out.data_ptr() == color.data_ptr():
+        raise RuntimeError(f"augment_color: out {tuple(out.shape)} on {out.device} must be another {tuple(color.shape)} tensor on {dev}")
+    check(lib().msm_augment_color(_p(color), _p(table), _p(noise), _p(out), _p(status), B, H, W, _stream()), "msm_augment_color")
+    return out
+
+
+def augment_depth(depth, table, status, *, depth_div=1000.0, records=None, stages=3, out=None):
+    """D4 of augment.py on a batch (msm_augment_depth, three launches): depth (B,H,W) uint16 / int16 bits (z = d / depth_div) or float32
+    (metres, NaN -> 0), table and status as augment_color (column 1 is written) -> (out (B,H,W) float32, new or given, records).  ``records``
+    (int32, msm_augment_depth_workspace bytes: B blocks of AUGMENT_RECORD_ROW words, then the row counts) and ``stages`` (1: row
+    counts and centres, 2: apply, 3: all) are for tests of the last launch on hand-made records."""
+    if depth.dtype not in _DEPTH_U16 + (torch.float32,):
+        raise RuntimeError(f"augment_depth: depth must be uint16 (or int16 bits) or float32, got {depth.dtype}")
+    _c(depth, "depth", depth.dtype)
+    if depth.dim() != 3 or 0 in depth.shape:
+        raise RuntimeError(f"augment_depth: depth {tuple(depth.shape)} must be a non-empty (B, H, W)")
+    B, H, W = depth.shape
+    dev = depth.device
+    _check_augment_table(table, status, B, dev, "augment_depth")
+    nbytes = lib().msm_augment_depth_workspace(B, H, W)
+    if nbytes < 0:
+        check(int(nbytes), "msm_augment_depth_workspace")
+    if records is None:
+        records = torch.empty((nbytes // 4,), device=dev, dtype=torch.int32)
+    _c(records, "records", torch.int32)
+    if records.numel() * 4 < nbytes or records.device != dev:
+        raise RuntimeError(f"augment_depth: records of {records.numel() * 4} bytes on {records.device}, {nbytes} needed on {dev}")
+    if out is None:
+        out = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    _c(out, "out")
+    if tuple(out.shape) != (B, H, W) or out.device != dev:
+        raise RuntimeError(f"augment_depth: out {tuple(out.shape)} on {out.device} must be {(B, H, W)} on {dev}")
+    check(lib().msm_augment_depth(_p(depth), 1 if depth.dtype in _DEPTH_U16 else 0, float(depth_div), _p(table), _p(out), _p(status),
+                                  _p(records), records.numel() * 4, int(stages), B, H, W, _stream()), "msm_augment_depth")
+    return out, records
+
+
+def xyz_noise_(xyz, gp, taps, scale, size=None):
+    """D5 of augment.py in place in one launch (msm_xyz_noise): xyz (B,3,Hp,Wp) float32, gp (B,3,h,w) float32, taps (H + W, 8)
+    int32 (augment._device_taps), ``size`` = (H, W) the valid corner (default the whole map).  Returns xyz."""
+    _c(xyz, "xyz"), _c(gp, "gp"), _c(taps, "taps", torch.int32)
+    if xyz.dim() != 4 or xyz.shape[1] != 3 or 0 in xyz.shape:
+        raise RuntimeError(f"xyz_noise_: xyz {tuple(xyz.shape)} must be a non-empty (B, 3, Hp, Wp)")
+    B, _, Hp, Wp = xyz.shape
+    H, W = (Hp, Wp) if size is None else (int(size[0]), int(size[1]))
+    if gp.dim() != 4 or tuple(gp.shape[:2]) != (B, 3) or 0 in gp.shape or gp.device != xyz.device:
+        raise RuntimeError(f"xyz_noise_: gp {tuple(gp.shape)} on {gp.device} must be ({B}, 3, h, w) on {xyz.device}")
+    if not (0 < H <= Hp and 0 < W <= Wp) or tuple(taps.shape) != (H + W, 8) or taps.device != xyz.device:
+        raise RuntimeError(f"xyz_noise_: size {(H, W)} must lie inside {(Hp, Wp)} and taps {tuple(taps.shape)} be ({H + W}, 8)")
+    check(lib().msm_xyz_noise(_p(xyz), _p(gp), _p(taps), float(scale), B, H, W, Hp, Wp, gp.shape[2], gp.shape[3], _stream()),
+          "msm_xyz_noise")
+    return xyz
+
+
 # ----------------------------------------------------------------------------------------------
 # backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------

@@ -357,13 +357,25 @@ def sample_pixels(labels, num=1000, *, keys=None, generator=None):
     return out[0] if single else out
 
 
-def training_batch(color, depth, raw, camera_params, *, size_divisibility=1, order="bgr", depth_scale=1000.0, **target_args):
+def training_batch(color, depth, raw, camera_params, *, size_divisibility=1, order="bgr", depth_scale=1000.0, augment=None,
+                   **target_args):
     """Raw frames and their label images -> (image, xyz, TargetBatch): frames.ingest and instance_targets padded to the same
     ``size_divisibility``.  ``training.ucn_model_losses(model, image, xyz, batch.targets, criterion, labels=batch.label, ...)``
-    (or ``batch`` itself in place of ``batch.targets``) takes them as they are.  ``target_args``: instance_targets' keywords."""
+    (or ``batch`` itself in place of ``batch.targets``) takes them as they are.  ``target_args``: instance_targets' keywords.
+    ``augment``: an augment.AugmentParams (augment.draw_params) living where the frames live -- the loader's random
+    augmentations in the reference's order: the colour frames (in the order they arrive in; the reference's are BGR), the
+    depth (scaled and with ellipses dropped, float32 metres from there on), ingest, then the point-cloud noise on the valid
+    corner of xyz.  The label images are not touched, as in the reference.  None: exactly the launches without it."""
     if color.ndim != 4 or raw.ndim != 3 or tuple(raw.shape) != tuple(color.shape[:3]):
         raise ValueError(f"training_batch: colour {tuple(color.shape)} must be (B, H, W, 3) and raw {tuple(raw.shape)} (B, H, W)")
     if _is_device(color) != _is_device(raw):
         raise ValueError("training_batch: frames and label images must live on the same side")
+    if augment is not None:
+        from . import augment as aug
+        color = aug.augment_color(color, augment)
+        if depth is not None:
+            depth, depth_scale = aug.augment_depth(depth, augment, depth_scale=depth_scale), 1.0
     image, xyz = frames.ingest(color, depth, camera_params, order=order, depth_scale=depth_scale, size_divisibility=size_divisibility)
+    if augment is not None and xyz is not None and augment.gp_noise is not None:
+        aug.add_xyz_noise_(xyz, augment, size=tuple(color.shape[1:3]))
     return image, xyz, instance_targets(raw, size_divisibility=size_divisibility, **target_args)
