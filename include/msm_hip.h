@@ -60,6 +60,8 @@
  *   msm_augment_* / msm_xyz_noise
  *                                <- chromatic_transform / add_noise lib/utils/blob.py:74-129, add_noise_to_depth /
  *                                   dropout_random_ellipses / add_noise_to_xyz lib/utils/augmentation.py:58-126
+ *   msm_crop_boxes / msm_train_crop
+ *                                <- TableTopDataset.pad_crop_resize lib/datasets/tabletop_dataset.py:234-300,354-358 (TRAIN.SYN_CROP)
  *   msm_optim_*                  <- Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191: clip_grad_norm_ over
  *                                   the whole model, then torch.optim.AdamW with one param group per tensor
  */
@@ -78,7 +80,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 41   /* 41: msm_augment_color / msm_augment_depth + msm_augment_depth_workspace / msm_xyz_noise, msm_augment_table_row (the training loader's random augmentations of a batch on the device: HLS shift, pixel noise, motion blur, depth scaling and ellipse dropout, point-cloud noise); 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 42   /* 42: msm_crop_boxes / msm_train_crop (the SYN_CROP training path on the device: one object box per frame, squared and padded, then colour, label and xyz cropped there and resized to S x S in one launch); 41: msm_augment_color / msm_augment_depth + msm_augment_depth_workspace / msm_xyz_noise, msm_augment_table_row (the training loader's random augmentations of a batch on the device: HLS shift, pixel noise, motion blur, depth scaling and ellipse dropout, point-cloud noise); 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1437,6 +1439,58 @@ int msm_augment_depth(const void* depth, int depth_is_u16, float depth_div, cons
                       void* workspace, int64_t workspace_bytes, int stages, int B, int H, int W, void* stream);
 int msm_xyz_noise(float* xyz, const float* gp, const int32_t* taps, float scale, int B, int H, int W, int Hp, int Wp, int h, int w,
                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training crops (TRAIN.SYN_CROP: TableTopDataset.pad_crop_resize lib/datasets/tabletop_dataset.py:234-300,354-358) for a batch:
+ * one object per frame, its box squared, padded by a random fraction and clamped to the image; colour, label image and xyz cropped
+ * there and resized to S x S.  The two random numbers per frame are drawn by the caller; the kernels are pure functions.  The
+ * reference resizes with cv2; the definitions are this library's own, the numpy host path of crops.py states them a second time,
+ * and the two agree bit for bit.  Every step is an integer step or a float64 step on small half-integers (exact), except the one
+ * product of C2.
+ *
+ * msm_crop_boxes: one launch, one lane per image; reads the image's row of msm_target_tables (the tables of the FULL frames, built
+ *   with the call's background ids) and writes one box row.  No pixel is read: the tight boxes are in the table.
+ *   params [B][2] int32 words: key (uint32), p (float bits): the padding fraction, 0 <= p <= 16
+ *   boxes  [B][MSM_CROP_BOX_ROW] int32: x0, y0, x1, y1 (inclusive), the chosen dense index, the chosen raw id (-1: none), the
+ *          padding, status bits
+ *   C1  K = K_b - 1 (the reference's np.max of the dense map).  K > 0: dense index idx = 1 + ((uint64(key) * K) >> 32), instance row
+ *       t = idx - (K_b - T_b), the region's tight box is that instance record's.  K <= 0 (background only, or one value everywhere):
+ *       the region is the whole image, box (0, 0, W - 1, H - 1), idx 0, id -1.
+ *   C2  (float64, the reference's order)  cx = (x_min + x_max) / 2, cy likewise; x_delta = x_max - x_min, y_delta likewise;
+ *       x_delta > y_delta: y_min, y_max = cy -+ x_delta / 2, else x_min, x_max = cx -+ y_delta / 2; side = x_max - x_min;
+ *       padding = int(rint(side * double(p))) (ties to even), 0 -> 25; x0 = max(trunc(x_min - padding), 0),
+ *       x1 = min(trunc(x_max + padding), W - 1), y0 and y1 likewise with H (trunc rounds toward zero).
+ *       With H, W >= 2 this always gives x0 < x1 and y0 < y1 (the box centre lies inside the image and padding >= 1): the
+ *       reference's redraw never happens.  Should it not hold, MSM_CROP_DEGENERATE is set and the box is the whole image.
+ *   MSM_CROP_BAD_ROW: p is not in [0, 16] (or not a number), or the table row contradicts itself (an instance row outside
+ *       [0, T_b), a record box outside the image): the box is the whole image, idx 0, id -1, padding 0.  No index taken from a
+ *       table is used before it is bounded.
+ *   B <= 65535, H, W >= 2, H W <= 2^24.
+ *
+ * msm_train_crop: one launch for the three outputs; a workgroup per (image, band of 8 output rows), the S column records (taps,
+ *   weight, nearest index) once per workgroup in LDS, the row records wave-uniform, four consecutive output pixels per lane.
+ *   color [B][H][W][3] uint8, raw [B][H][W] uint8 or int32 (raw_is_i32), xyz [B][3][Hp][Wp] float or NULL (then xyz_out NULL too)
+ *   color_out [B][S][S][3] uint8, raw_out [B][S][S] of raw's type, xyz_out [B][3][Sp][Sp] float, zero in rows and columns >= S
+ *   With n_x = x1 - x0 + 1 and n_y = y1 - y0 + 1 of the image's box:
+ *   C3  nearest (raw ids, kept as they are; xyz bit for bit): s(d) = (d * n) / S in integers; output (dy, dx) reads source
+ *       (y0 + s_y(dy), x0 + s_x(dx)).
+ *   C4  bilinear (colour), half-pixel centres, integers only: num = (2 d + 1) n - S; s = floor(num / (2 S)); frac = num - 2 S s;
+ *       w1 = (frac * 2048 + S) / (2 S), w0 = 2048 - w1; s < 0: s = 0, w1 = 0; s >= n - 1: s = n - 1, w1 = 0; the second tap is
+ *       min(s + 1, n - 1).  Per channel out = ((a wx0 + b wx1) wy0 + (c wx0 + d wx1) wy1 + 2^21) >> 22 (below 2^31).
+ *   Every image's box is validated before use (0 <= x0 < x1 <= W - 1, 0 <= y0 < y1 <= H - 1); an invalid row writes zeros to the
+ *   three outputs of its image and ORs MSM_CROP_BAD_BOX into boxes[b][7]; the other images are not affected.
+ *   Stores: 16 bytes per lane (xyz, int32 labels; 12 for colour, 4 for uint8 labels) where S % 4 == 0, Sp % 4 == 0 and the outputs
+ *   are 16-byte aligned, element-wise otherwise: the same values either way.
+ *   B <= 65535, H, W >= 2, H W <= 2^24, 1 <= S <= Sp, S <= MSM_CROP_MAX_SIZE, Sp <= 2 MSM_CROP_MAX_SIZE, with xyz Hp >= H, Wp >= W,
+ *   Hp Wp <= 2^26; else MSM_E_INVALID. */
+#define MSM_CROP_BOX_ROW 8
+#define MSM_CROP_MAX_SIZE 1024
+#define MSM_CROP_DEGENERATE 1
+#define MSM_CROP_BAD_BOX 2
+#define MSM_CROP_BAD_ROW 4
+int msm_crop_boxes(const int32_t* tables, const int32_t* params, int32_t* boxes, int B, int H, int W, void* stream);
+int msm_train_crop(const uint8_t* color, const void* raw, int raw_is_i32, const float* xyz, int32_t* boxes, uint8_t* color_out,
+                   void* raw_out, float* xyz_out, int B, int H, int W, int Hp, int Wp, int S, int Sp, void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,8 +52,9 @@ read or write outside its buffers.
 
 Like frames and targets, the functions follow their data: device tensors go through the HIP kernels (ops.augment_color,
 ops.augment_depth, ops.xyz_noise_), host tensors and numpy arrays through the definitions in numpy.  There is no fallback on a
-device tensor.  Not included: pad_crop_resize / TRAIN.SYN_CROP, the label augmentations of augmentation.py:195-509 (no MSMFormer
-config uses them), random numbers inside kernels, equality with cv2.
+device tensor.  pad_crop_resize / TRAIN.SYN_CROP lives in crops.py; with targets.training_batch(..., crop=) the colour half
+of an AugmentParams applies to the S x S crops and is drawn at that size.  Not included: the label augmentations of
+augmentation.py:195-509 (no MSMFormer config uses them), random numbers inside kernels, equality with cv2.
 """
 import numpy as np
 import torch

@@ -2245,6 +2245,73 @@ def xyz_noise_(xyz, gp, taps, scale, size=None):
     return xyz
 
 
+# ---- training crops, TRAIN.SYN_CROP (crops.py; csrc/train_crop.hip) ----
+CROP_BOX_ROW = 8             # MSM_CROP_BOX_ROW: x0, y0, x1, y1, dense index, raw id, padding, status bits
+CROP_MAX_SIZE = 1024         # MSM_CROP_MAX_SIZE
+CROP_DEGENERATE, CROP_BAD_BOX, CROP_BAD_ROW = 1, 2, 4      # MSM_CROP_* bits of boxes[b][7]
+
+
+def crop_boxes(tables, params, image_size, *, out=None):
+    """One crop box per image in one launch (msm_crop_boxes): tables (B, row) int32 as target_tables returned them for the FULL
+    frames, params (B,2) int32 words -- a uint32 key and the bits of the float32 padding fraction -- ``image_size`` = (H, W) ->
+    boxes (B, CROP_BOX_ROW) int32 (new, or ``out``): x0, y0, x1, y1 inclusive, the chosen dense index and raw id, the padding,
+    status bits.  Nothing here waits."""
+    _c(tables, "tables", torch.int32), _c(params, "params", torch.int32)
+    H, W = int(image_size[0]), int(image_size[1])
+    if tables.dim() != 2 or tables.shape[0] == 0 or tables.shape[1] != lib().msm_target_table_row():
+        raise RuntimeError(f"crop_boxes: tables {tuple(tables.shape)} must be a non-empty (B, {lib().msm_target_table_row()})")
+    B, dev = tables.shape[0], tables.device
+    if tuple(params.shape) != (B, 2) or params.device != dev:
+        raise RuntimeError(f"crop_boxes: params {tuple(params.shape)} on {params.device} must be ({B}, 2) on {dev}")
+    if out is None:
+        out = torch.empty((B, CROP_BOX_ROW), device=dev, dtype=torch.int32)
+    _c(out, "out", torch.int32)
+    if tuple(out.shape) != (B, CROP_BOX_ROW) or out.device != dev:
+        raise RuntimeError(f"crop_boxes: out {tuple(out.shape)} on {out.device} must be ({B}, {CROP_BOX_ROW}) on {dev}")
+    check(lib().msm_crop_boxes(_p(tables), _p(params), _p(out), B, H, W, _stream()), "msm_crop_boxes")
+    return out
+
+
+def train_crop(color, raw, xyz, boxes, size, *, frame=None, out_color=None, out_raw=None, out_xyz=None):
+    """Crop and resize a batch in one launch (msm_train_crop): color (B,H,W,3) uint8 (bilinear, C4 of crops.py), raw (B,H,W) uint8
+    or int32 (nearest, ids kept) and xyz (B,3,Hp,Wp) float32 or None (nearest, bit for bit), each inside its image's row of
+    ``boxes`` (B, CROP_BOX_ROW) int32, resized to ``size`` = S -> (color (B,S,S,3), raw (B,S,S), xyz (B,3,Sp,Sp) or None), Sp =
+    ``frame`` (default S), zeros beyond S.  A row whose box does not lie inside the image gives zeros and gets CROP_BAD_BOX ORed
+    into boxes[b][7].  ``out_*``: contiguous tensors to write into."""
+    _c(color, "color", torch.uint8), _c(xyz, "xyz"), _c(boxes, "boxes", torch.int32)
+    _check_raw(raw, "train_crop")
+    if color.dim() != 4 or color.shape[-1] != 3 or tuple(color.shape[:3]) != tuple(raw.shape) or raw.device != color.device:
+        raise RuntimeError(f"train_crop: color {tuple(color.shape)} must be (B, H, W, 3) and raw {tuple(raw.shape)} (B, H, W) beside it")
+    B, H, W = raw.shape
+    dev = color.device
+    S = int(size)
+    Sp = S if frame is None else int(frame)
+    if tuple(boxes.shape) != (B, CROP_BOX_ROW) or boxes.device != dev:
+        raise RuntimeError(f"train_crop: boxes {tuple(boxes.shape)} on {boxes.device} must be ({B}, {CROP_BOX_ROW}) on {dev}")
+    Hp, Wp = H, W
+    if xyz is not None:
+        if xyz.dim() != 4 or tuple(xyz.shape[:2]) != (B, 3) or xyz.device != dev:
+            raise RuntimeError(f"train_crop: xyz {tuple(xyz.shape)} on {xyz.device} must be ({B}, 3, Hp, Wp) on {dev}")
+        Hp, Wp = xyz.shape[2:]
+    elif out_xyz is not None:
+        raise RuntimeError("train_crop: out_xyz without xyz")
+    if not 1 <= S <= Sp:
+        raise RuntimeError(f"train_crop: size {S} must lie in [1, frame = {Sp}]")
+    outs = []
+    for t, name, shape, dtype in ((out_color, "out_color", (B, S, S, 3), torch.uint8), (out_raw, "out_raw", (B, S, S), raw.dtype),
+                                  (out_xyz, "out_xyz", (B, 3, Sp, Sp), torch.float32)):
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype) if (name != "out_xyz" or xyz is not None) else None
+        else:
+            _c(t, name, dtype)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError(f"train_crop: {name} {tuple(t.shape)} on {t.device} must be {shape} on {dev}")
+        outs.append(t)
+    check(lib().msm_train_crop(_p(color), _p(raw), 1 if raw.dtype == torch.int32 else 0, _p(xyz), _p(boxes), _p(outs[0]), _p(outs[1]),
+                               _p(outs[2]), B, H, W, Hp, Wp, S, Sp, _stream()), "msm_train_crop")
+    return tuple(outs)
+
+
 # ----------------------------------------------------------------------------------------------
 # backbone glue (csrc/backbone_ops.hip)
 # ----------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@ Own counterpart of what the reference builds per image on the host, same names w
                              TabletopDatasetMapper.__call__ lib/datasets/tablet_instance_mapper.py:140-175 (masks and classes per
                              image) and prepare_targets / ImageList.from_tensors of the label map,
                              MSMFormer/meanshiftformer/pretrained_meanshiftformer_model.py:319-321,380-395 (zero padding)
-  training_batch          <- frames.ingest + instance_targets: the arguments of training.ucn_model_losses
+  training_batch          <- frames.ingest + instance_targets: the arguments of training.ucn_model_losses; with ``crop=`` the
+                             TRAIN.SYN_CROP path of __getitem__ :354-358 in between (crops.py)
 
 Definitions (every value an integer or an exact 0 / 1), per image of ``raw`` (B,H,W) uint8 or int32, ids in [0, 1024):
 
@@ -144,6 +145,7 @@ class TargetBatch:
     sampler does not handle.  It synchronises; instance_targets itself does not when ``counts`` is given."""
 
     is_target_batch = True
+    crop_boxes = None            # training_batch(..., crop=): the (B, 8) int32 box rows of crops.crop_boxes
 
     def __init__(self, masks, labels, boxes, ids, areas, label, counts, image_size, status=None, sample_status=None):
         self.masks, self.labels, self.boxes, self.ids, self.areas, self.label = masks, labels, boxes, ids, areas, label
@@ -358,18 +360,32 @@ def sample_pixels(labels, num=1000, *, keys=None, generator=None):
 
 
 def training_batch(color, depth, raw, camera_params, *, size_divisibility=1, order="bgr", depth_scale=1000.0, augment=None,
-                   **target_args):
+                   crop=None, crop_size=224, **target_args):
     """Raw frames and their label images -> (image, xyz, TargetBatch): frames.ingest and instance_targets padded to the same
     ``size_divisibility``.  ``training.ucn_model_losses(model, image, xyz, batch.targets, criterion, labels=batch.label, ...)``
     (or ``batch`` itself in place of ``batch.targets``) takes them as they are.  ``target_args``: instance_targets' keywords.
     ``augment``: an augment.AugmentParams (augment.draw_params) living where the frames live -- the loader's random
     augmentations in the reference's order: the colour frames (in the order they arrive in; the reference's are BGR), the
     depth (scaled and with ellipses dropped, float32 metres from there on), ingest, then the point-cloud noise on the valid
-    corner of xyz.  The label images are not touched, as in the reference.  None: exactly the launches without it."""
+    corner of xyz.  The label images are not touched, as in the reference.  None: exactly the launches without it.
+    ``crop``: a crops.CropParams (crops.draw_crop_params) living where the frames live -- the reference's TRAIN.SYN_CROP path
+    that trains the second-stage model, in its order (tabletop_dataset.py:349-367): depth augmentation, ingest at FULL
+    resolution for xyz, point-cloud noise, then one object per frame is chosen, its box squared, padded and clamped, colour,
+    label image and xyz are cropped there and resized to ``crop_size`` = S (crops.crop_boxes, crops.crop_resize),
+    instance_targets runs on the label crops (``sample_num`` and its keys at S x S), the colour augmentation on the S x S colour
+    crops, and frames.ingest turns those into the image.  Everything comes back at (B, 3, Sp, Sp), ``batch.image_size == (S, S)``
+    and ``batch.crop_boxes`` holds the boxes.  The colour half of ``augment`` is therefore drawn at the crop size
+    (``pixel_noise`` (B,S,S): anything else raises ValueError before a launch) and its ``gp_noise`` for the frame size:
+    augment.draw_params(B, S, S, ...) for the former and (B, 3, H // 4, W // 4) for the latter.  The only wait remains
+    instance_targets' count copy; ``counts=`` cannot be known before the crop is taken -- an object that leaves the crop leaves
+    the targets -- so a loader has none to give here.  None: exactly the launches without it."""
     if color.ndim != 4 or raw.ndim != 3 or tuple(raw.shape) != tuple(color.shape[:3]):
         raise ValueError(f"training_batch: colour {tuple(color.shape)} must be (B, H, W, 3) and raw {tuple(raw.shape)} (B, H, W)")
     if _is_device(color) != _is_device(raw):
         raise ValueError("training_batch: frames and label images must live on the same side")
+    if crop is not None:
+        return _training_batch_crop(color, depth, raw, camera_params, size_divisibility, order, depth_scale, augment, crop,
+                                    int(crop_size), target_args)
     if augment is not None:
         from . import augment as aug
         color = aug.augment_color(color, augment)
@@ -379,3 +395,33 @@ def training_batch(color, depth, raw, camera_params, *, size_divisibility=1, ord
     if augment is not None and xyz is not None and augment.gp_noise is not None:
         aug.add_xyz_noise_(xyz, augment, size=tuple(color.shape[1:3]))
     return image, xyz, instance_targets(raw, size_divisibility=size_divisibility, **target_args)
+
+
+def _training_batch_crop(color, depth, raw, camera_params, size_divisibility, order, depth_scale, augment, crop, S, target_args):
+    """training_batch with ``crop=``: the order of its docstring."""
+    from . import crops
+    B, H, W = raw.shape
+    if len(crop) != B:
+        raise ValueError(f"training_batch: {len(crop)} crop parameter rows for {B} frames")
+    if augment is not None:
+        from . import augment as aug
+        if augment.pixel_noise is not None and tuple(augment.pixel_noise.shape) != (B, S, S):
+            raise ValueError(f"training_batch: with crop= the colour augmentation runs on the {S} x {S} crops: pixel_noise "
+                             f"{tuple(augment.pixel_noise.shape)} must be {(B, S, S)} (draw the colour half at the crop size)")
+        if depth is not None:
+            depth, depth_scale = aug.augment_depth(depth, augment, depth_scale=depth_scale), 1.0
+    xyz = None
+    if depth is not None:
+        xyz = frames.ingest(color, depth, camera_params, order=order, depth_scale=depth_scale)[1]
+        if augment is not None and augment.gp_noise is not None:
+            aug.add_xyz_noise_(xyz, augment, size=(H, W))
+    boxes = crops.crop_boxes(raw, crop, background_ids=target_args.get("background_ids", BACKGROUND_IDS))
+    color_crop, raw_crop, xyz_crop = crops.crop_resize(color, raw, xyz, boxes, S, size_divisibility=size_divisibility)
+    batch = instance_targets(raw_crop, size_divisibility=size_divisibility, **target_args)
+    batch.crop_boxes = boxes
+    if augment is not None:
+        color_crop = aug.augment_color(color_crop, augment)
+    image = frames.ingest(color_crop, None, None, order=order, size_divisibility=size_divisibility)[0]
+    if isinstance(xyz_crop, np.ndarray):                   # host arrays: a tensor, as frames.ingest returns its xyz
+        xyz_crop = torch.from_numpy(xyz_crop)
+    return image, xyz_crop, batch
