@@ -1950,6 +1950,52 @@ def optim_adamw_step(tensors, chunks, hyper, partials, state, n_tensors, n_chunk
                                      float(max_norm), _stream()), "msm_optim_adamw_step")
 
 
+OPTIM_RULES = {"adamw": 0, "adam": 1, "sgd": 2}        # MSM_OPTIM_ADAMW, MSM_OPTIM_ADAM, MSM_OPTIM_SGD
+# hyper-parameter row of the rule entries: lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov
+
+
+def _optim_scalar(t, name, device):
+    """grad_scale / found_inf as GradScaler sets them: one float32 on the tables' device, or None.  The value is never read here."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != device:
+        raise RuntimeError(f"optimizer: {name} must be one torch.float32 element on {device}, got "
+                           f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else
+                           f"optimizer: {name} must be a tensor, got {type(t).__name__}")
+    return t.data_ptr()
+
+
+def optim_count_norm(tensors, chunks, partials, steps, n_tensors, n_chunks, n_rows, grad_scale=None, found_inf=None):
+    """msm_optim_count_norm: partials[c] = sum of (g / grad_scale)^2 over chunk c (double) and steps[row] += 1 for every tensor of
+    the table unless found_inf says the step is skipped, one launch.  steps int64 (n_rows,)."""
+    _optim_tables(tensors, chunks, n_tensors, n_chunks)
+    _c(partials, "partials", torch.float64), _c(steps, "steps", torch.int64)
+    if partials.numel() < n_chunks or n_rows < 1 or steps.numel() < n_rows:
+        raise RuntimeError(f"optim_count_norm: partials needs {n_chunks} doubles (got {partials.numel()}), steps {n_rows} int64 "
+                           f"(got {steps.numel()})")
+    check(lib().msm_optim_count_norm(_p(tensors), _p(chunks), _p(partials), _p(steps), _optim_scalar(grad_scale, "grad_scale", tensors.device),
+                                     _optim_scalar(found_inf, "found_inf", tensors.device), n_tensors, n_chunks, n_rows, _stream()),
+          "msm_optim_count_norm")
+
+
+def optim_update(rule, tensors, chunks, hyper, partials, state, steps, n_tensors, n_chunks, n_rows, max_norm, grad_scale=None,
+                 found_inf=None):
+    """msm_optim_update: the update of `rule` ("adamw", "adam", "sgd") on every chunk with step = steps[row], the gradient unscaled
+    by grad_scale and the whole step skipped on found_inf, one launch (two with max_norm <= 0: the counts move in a launch of their
+    own and partials may be None).  hyper float64 (n_rows, 8), state int64 (2,), steps int64 (n_rows,)."""
+    _optim_tables(tensors, chunks, n_tensors, n_chunks)
+    _c(hyper, "hyper", torch.float64), _c(partials, "partials", torch.float64), _c(state, "state", torch.int64)
+    _c(steps, "steps", torch.int64)
+    if n_rows < 1 or hyper.numel() < n_rows * OPTIM_HYP or state.numel() < 2 or steps.numel() < n_rows or (
+            max_norm > 0 and (partials is None or partials.numel() < n_chunks)):
+        raise RuntimeError(f"optim_update: {n_rows} rows need {n_rows * OPTIM_HYP} doubles (got {hyper.numel()}) and {n_rows} step "
+                           f"counts (got {steps.numel()}), state 2 int64, max_norm > 0 partials of {n_chunks} doubles")
+    check(lib().msm_optim_update(OPTIM_RULES[rule], _p(tensors), _p(chunks), _p(hyper), _p(partials), _p(state), _p(steps),
+                                 _optim_scalar(grad_scale, "grad_scale", tensors.device),
+                                 _optim_scalar(found_inf, "found_inf", tensors.device), n_tensors, n_chunks, n_rows, float(max_norm),
+                                 _stream()), "msm_optim_update")
+
+
 def optim_zero(tensors, chunks, n_tensors, n_chunks):
     """msm_optim_zero: g = 0 for every chunk of the table, one launch."""
     _optim_tables(tensors, chunks, n_tensors, n_chunks)

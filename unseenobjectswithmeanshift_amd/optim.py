@@ -10,6 +10,14 @@ update per chunk (the definition is in include/msm_hip.h).  Nothing in ``step()`
     optimizer = build_optimizer(model.sem_seg_head, base_lr=1e-4)       # = FullModelClipAdamW(build_param_groups(...), ...)
     sum(losses.values()).backward(); optimizer.step(); optimizer.zero_grad()
 
+``SGD`` and ``Adam`` are the optimizers of the UCN embedding network (tools/train_net.py:130-142: two param groups, biases then
+weights; ``build_ucn_optimizer``) on the same table, chunk list and uploads, through the rule entries of the library
+(msm_optim_count_norm / msm_optim_update), which keep the step count of every tensor on the device.  All three classes follow
+GradScaler's protocol for fused optimizers (``_step_supports_amp_scaling``: the scaler sets ``grad_scale`` and ``found_inf``, the
+kernels unscale and skip), so the reference's ``grad_scaler.step(optimizer)`` (AMPTrainer.run_step, :209-246) does not wait either:
+
+    scaler.scale(losses).backward(); scaler.step(optimizer); scaler.update()
+
 No CPU path and no fallback: parameters and gradients are contiguous float32 tensors on one GPU.
 """
 import operator
@@ -52,6 +60,7 @@ def build_param_groups(model, base_lr, weight_decay=0.05, weight_decay_norm=0.0,
 
 
 _HYPER = operator.itemgetter("lr", "weight_decay", "betas", "eps", "amsgrad", "maximize")
+_SGD_HYPER = operator.itemgetter("lr", "weight_decay", "momentum", "dampening", "nesterov", "maximize")
 _DATA_PTR = torch.Tensor.data_ptr
 
 
@@ -65,60 +74,39 @@ class _Slot:
         self.event = None
 
 
-class FullModelClipAdamW(torch.optim.Optimizer):
-    """``torch.optim.AdamW`` behind ``torch.nn.utils.clip_grad_norm_(all parameters, max_norm)``, two launches per ``step()``.
+class _TableOptimizer(torch.optim.Optimizer):
+    """What the three optimizers share: the device table (hyper rows, tensor records, chunk list), its host mirror and uploads, the
+    launches of a step, ``zero_grad`` in one launch, the state dicts.  A subclass names its rule, the hyper-parameters of a group
+    (``_hyper_of``, ``_group_rows``) and its per-parameter state (``_state_of``, ``_write_counts``, ``_loaded_counts``).
 
-    ``params``, ``lr``, ``betas``, ``eps``, ``weight_decay`` and ``param_groups`` are torch's: a scheduler that writes
-    ``group["lr"]`` works unchanged, and ``state_dict()`` / ``load_state_dict()`` are interchangeable with ``torch.optim.AdamW`` over
-    the same groups (per parameter ``step``, ``exp_avg``, ``exp_avg_sq``).  ``max_norm <= 0`` turns the clipping off.  A parameter
-    whose ``.grad`` is None is left out of the step as torch leaves it out: no norm contribution, no state change, no step count.
+    Step counts: with ``_device_counts`` they live in ``_steps_dev`` (int64 per parameter), advanced by the launches for the tensors
+    that take a step, and the step goes through the rule entries, which also take GradScaler's ``grad_scale`` / ``found_inf``.
+    Without (``FullModelClipAdamW`` until it first meets a scaler) the host derives them from the call counter, as it always did."""
 
-    The host keeps what it last uploaded -- the hyper-parameters of every group and the addresses of every parameter and
-    gradient -- and uploads again, in one asynchronous copy from pinned staging, only when one of them changed: a scheduler's lr
-    (the 64-byte rows alone), a gradient reallocated after ``zero_grad(set_to_none=True)`` or a parameter without a gradient (the
-    whole table).  ``uploads`` counts the copies.  ``step()`` copies nothing back, never synchronises and allocates nothing after
-    the first call with a given set of gradients; ``zero_grad(set_to_none=False)`` is one launch over the same table.
-    ``last_grad_norm`` / ``last_clip_coef``: 0-d float32 device tensors (views of the kernels' state block) of the last step, the
-    norm before clipping; None before the first step, and with ``max_norm <= 0`` the norm is not computed and reads 0.
-    Everything is issued on the stream that is current when ``step()`` is called; use one stream for the steps of one optimizer.
+    _NAME = None
+    _RULE = None
+    _hyper_of = None
+    _step_supports_amp_scaling = True       # torch/amp/grad_scaler.py:403-454: the scaler sets grad_scale / found_inf and calls step()
 
-    Not supported (NotImplementedError): ``amsgrad``, ``maximize``, a ``closure``, parameters other than float32;
-    RuntimeError: host tensors, non-contiguous parameters or gradients, parameters on several devices."""
-
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 max_norm=0.01):
-        if amsgrad:
-            raise NotImplementedError("FullModelClipAdamW: amsgrad=True is not supported")
-        if maximize:
-            raise NotImplementedError("FullModelClipAdamW: maximize=True is not supported")
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid betas: {betas}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        # the keys of torch.optim.AdamW's own groups, so that a state dict of either loads into the other and then steps
-        defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)
-        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
+    def _setup(self, max_norm, device_counts):
         self.max_norm = float(max_norm)
         self.uploads = 0
         self.last_grad_norm = None
         self.last_clip_coef = None
-        self._calls = 0                 # value of the device call counter once everything issued has run
+        self._device_counts = device_counts
+        self._calls = 0                 # value of the device call counter once everything issued has run (host-counted steps)
         self._params = None             # flat parameter list; everything below is built from it at the first step
-        super().__init__(params, defaults)
+        self._seen = set()              # indices of the parameters that an earlier table held (their device counts may have moved)
 
     # ---- layout: what depends on the parameter list alone ----
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
         for p in self.param_groups[-1]["params"]:
             if p.dtype != torch.float32:
-                raise NotImplementedError(f"FullModelClipAdamW: parameter of shape {tuple(p.shape)} is {p.dtype}; only torch.float32 "
+                raise NotImplementedError(f"{self._NAME}: parameter of shape {tuple(p.shape)} is {p.dtype}; only torch.float32 "
                                           "parameters are supported")
             if not p.is_contiguous():
-                raise RuntimeError(f"FullModelClipAdamW: parameter of shape {tuple(p.shape)} is not contiguous")
+                raise RuntimeError(f"{self._NAME}: parameter of shape {tuple(p.shape)} is not contiguous")
         if getattr(self, "_params", None) is not None:
             self._layout(keep_offsets=True)
 
@@ -127,14 +115,14 @@ class FullModelClipAdamW(torch.optim.Optimizer):
         params = [p for g in self.param_groups for p in g["params"]]
         for p in params:
             if not p.is_cuda:
-                raise RuntimeError(f"FullModelClipAdamW: parameter of shape {tuple(p.shape)} must be on the GPU (no CPU path in "
+                raise RuntimeError(f"{self._NAME}: parameter of shape {tuple(p.shape)} must be on the GPU (no CPU path in "
                                    "unseenobjectswithmeanshift_amd)")
             if p.device != params[0].device:
-                raise RuntimeError(f"FullModelClipAdamW: parameters on {params[0].device} and {p.device}; one optimizer serves one GPU")
+                raise RuntimeError(f"{self._NAME}: parameters on {params[0].device} and {p.device}; one optimizer serves one GPU")
             if p.numel() == 0:
-                raise RuntimeError("FullModelClipAdamW: a parameter without elements")
+                raise RuntimeError(f"{self._NAME}: a parameter without elements")
         self._params = params
-        self._off = [old.get(id(p), self._calls) for p in params]           # step of parameter i = calls - off[i]
+        self._off = [old.get(id(p), self._calls) for p in params]           # step of parameter i = calls - off[i] (host-counted)
         self._group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
         chunk = self.chunk = ops.optim_chunk()
         self._chunk_offsets = [np.arange(0, p.numel(), chunk, dtype=np.int64) for p in params]
@@ -150,9 +138,16 @@ class FullModelClipAdamW(torch.optim.Optimizer):
         self._partials = torch.zeros(C, dtype=torch.float64, device=dev)
         if getattr(self, "_state_dev", None) is None or self._state_dev.device != dev:
             self._state_dev = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._state_dev[0] = self._calls
+            if self._calls:
+                self._state_dev[:1].fill_(self._calls)       # a launch: the first step may run where nothing may wait
             f = self._state_dev.view(torch.float32)
             self.last_grad_norm, self.last_clip_coef = f[2], f[3]
+        if self._device_counts:             # a parameter group added later: the counts of the parameters before it stay
+            steps = torch.zeros(T, dtype=torch.int64, device=dev)
+            before = getattr(self, "_steps_dev", None) if keep_offsets else None
+            if before is not None:
+                steps[:before.numel()].copy_(before)
+            self._steps_dev = steps
         self._slots = [_Slot(self._words), _Slot(self._words)]
         self._hyper_key = self._table_key = None
         self._present, self._absent = [], []
@@ -174,18 +169,27 @@ class FullModelClipAdamW(torch.optim.Optimizer):
         slot.event.record()
         self.uploads += 1
 
+    def _upload_counts(self, counts):
+        """The step counts of every parameter, known to the host at this moment, to the device: one asynchronous copy."""
+        staged = torch.tensor(counts, dtype=torch.int64).pin_memory()
+        self._steps_dev = staged.to(self._device, non_blocking=True)
+
     def _hyper_rows(self, key):
-        for gi, (lr, wd, betas, eps, amsgrad, maximize) in enumerate(key):
-            if amsgrad or maximize:
-                raise NotImplementedError(f"FullModelClipAdamW: param group {gi} sets {'amsgrad' if amsgrad else 'maximize'}")
-            if isinstance(lr, torch.Tensor) or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-                raise ValueError(f"FullModelClipAdamW: param group {gi}: lr must be a Python float and betas in [0, 1), got "
-                                 f"{type(lr).__name__}, {betas}")
-        per_group = np.array([(lr, wd, betas[0], betas[1], eps) for lr, wd, betas, eps, _, _ in key], dtype=np.float64)
         rows = np.zeros((len(self._params), ops.OPTIM_HYP), dtype=np.float64)
-        rows[:, :5] = per_group[self._group_of]
-        rows[:, 5] = self._off
+        rows[:] = self._group_rows(key)[self._group_of]
+        if not self._device_counts:
+            rows[:, 5] = self._off
         return rows.ravel()
+
+    def _table_extra(self):
+        """What besides the addresses decides the records (SGD: which groups keep a momentum buffer)."""
+        return ()
+
+    def _check_state(self, i, p, tensors):
+        for name, s in tensors:
+            if s.dtype != torch.float32 or s.device != self._device or s.shape != p.shape or not s.is_contiguous():
+                raise RuntimeError(f"{self._NAME}: state {name} of parameter {i} must be a contiguous float32 tensor of shape "
+                                   f"{tuple(p.shape)} on {self._device}")
 
     def _records(self, gptrs):
         """The tensor records and the chunk list of the parameters that have a gradient; creates their state."""
@@ -195,24 +199,14 @@ class FullModelClipAdamW(torch.optim.Optimizer):
             p = self._params[i]
             g = p.grad
             if not g.is_cuda or g.device != self._device:
-                raise RuntimeError(f"FullModelClipAdamW: the gradient of parameter {i} must be on the GPU ({self._device}), got {g.device}")
+                raise RuntimeError(f"{self._NAME}: the gradient of parameter {i} must be on the GPU ({self._device}), got {g.device}")
             if g.dtype != torch.float32 or g.is_sparse:
-                raise NotImplementedError(f"FullModelClipAdamW: the gradient of parameter {i} is {g.dtype}"
+                raise NotImplementedError(f"{self._NAME}: the gradient of parameter {i} is {g.dtype}"
                                           f"{' (sparse)' if g.is_sparse else ''}; only dense torch.float32 is supported")
             if not p.is_contiguous() or not g.is_contiguous():
-                raise RuntimeError(f"FullModelClipAdamW: parameter {i} of shape {tuple(p.shape)} or its gradient is not contiguous")
-            st = self.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                self._off[i] = self._calls
-            m, v = st["exp_avg"], st["exp_avg_sq"]
-            for name, s in (("exp_avg", m), ("exp_avg_sq", v)):
-                if s.dtype != torch.float32 or s.device != self._device or s.shape != p.shape or not s.is_contiguous():
-                    raise RuntimeError(f"FullModelClipAdamW: state {name} of parameter {i} must be a contiguous float32 tensor of shape "
-                                       f"{tuple(p.shape)} on {self._device}")
-            ptrs = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr())
+                raise RuntimeError(f"{self._NAME}: parameter {i} of shape {tuple(p.shape)} or its gradient is not contiguous")
+            m, v = self._state_of(i, p)
+            ptrs = (p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), 0 if v is None else v.data_ptr())
             flags = (ops.OPTIM_ALIGNED if all(a % 16 == 0 for a in ptrs) else 0) | (ops.OPTIM_ALIGNED_G if ptrs[1] % 16 == 0 else 0)
             rec[t] = (*ptrs, p.numel(), i, flags, 0)
         chunks = np.empty((sum(len(self._chunk_offsets[i]) for i in present), 2), dtype=np.int64)
@@ -229,9 +223,9 @@ class FullModelClipAdamW(torch.optim.Optimizer):
         if self._params is None:
             self._layout()
         params = self._params
-        hyper_key = list(map(_HYPER, self.param_groups))                # ~0.1 ms of Python per step for 298 groups: no
+        hyper_key = list(map(self._hyper_of, self.param_groups))        # ~0.1 ms of Python per step for 298 groups: no
         gptrs = [0 if g is None else g.data_ptr() for g in [p.grad for p in params]]      # per-group work beyond these lines
-        table_key = (gptrs, list(map(_DATA_PTR, params)))
+        table_key = (gptrs, list(map(_DATA_PTR, params)), self._table_extra())
         if table_key != self._table_key:
             present, rec, chunks = self._records(gptrs)
             seen = set(present)
@@ -240,6 +234,7 @@ class FullModelClipAdamW(torch.optim.Optimizer):
             slot.i64[self._rec0:self._rec0 + rec.size] = rec.ravel()
             slot.i64[self._chk0:self._chk0 + chunks.size] = chunks.ravel()
             self._present, self._absent = present, [i for i in range(len(params)) if i not in seen]
+            self._seen |= seen
             self._n_tensors, self._n_chunks = len(present), len(chunks)
             if present:
                 self._upload(slot, self._chk0 + chunks.size)
@@ -255,16 +250,33 @@ class FullModelClipAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
-            raise NotImplementedError("FullModelClipAdamW: a closure is not supported; compute the loss before step()")
+            raise NotImplementedError(f"{self._NAME}: a closure is not supported; compute the loss before step()")
+        # GradScaler.step sets these around the call (0-d float32 device tensors; grad_scale None after scaler.unscale_(optimizer)).
+        # Only their addresses are used: the kernels read the values.
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         with torch.cuda.device(self._device if self._params is not None else self._first_device()):
+            if not self._device_counts and (grad_scale is not None or found_inf is not None):
+                # a skipped step is decided on the device, where the host's call counter cannot follow: from here on the counts
+                # live there.  The host knows them exactly at this moment.
+                if self._params is None:
+                    self._layout()
+                self._upload_counts([self._calls - o for o in self._off])
+                self._device_counts = True
+                self._hyper_key = None
             self._prepare()
             if not self._n_tensors:
                 return None
-            n, c = self._n_tensors, self._n_chunks
+            n, c, rows = self._n_tensors, self._n_chunks, len(self._params)
+            if self._device_counts:
+                if self.max_norm > 0:
+                    ops.optim_count_norm(self._rec_dev, self._chk_dev, self._partials, self._steps_dev, n, c, rows, grad_scale, found_inf)
+                ops.optim_update(self._RULE, self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev,
+                                 self._steps_dev, n, c, rows, self.max_norm, grad_scale, found_inf)
+                return None
             if self.max_norm > 0:
                 ops.optim_grad_norm(self._rec_dev, self._chk_dev, self._partials, self._state_dev, n, c)
-            ops.optim_adamw_step(self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev, n, c,
-                                 len(self._params), self.max_norm)
+            ops.optim_adamw_step(self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev, n, c, rows,
+                                 self.max_norm)
         self._calls += 1
         for i in self._absent:              # the counter moved, their step did not
             self._off[i] += 1
@@ -274,10 +286,10 @@ class FullModelClipAdamW(torch.optim.Optimizer):
         for g in self.param_groups:
             for p in g["params"]:
                 if not p.is_cuda:
-                    raise RuntimeError(f"FullModelClipAdamW: parameter of shape {tuple(p.shape)} must be on the GPU (no CPU path in "
+                    raise RuntimeError(f"{self._NAME}: parameter of shape {tuple(p.shape)} must be on the GPU (no CPU path in "
                                        "unseenobjectswithmeanshift_amd)")
                 return p.device
-        raise RuntimeError("FullModelClipAdamW: no parameters")
+        raise RuntimeError(f"{self._NAME}: no parameters")
 
     def zero_grad(self, set_to_none=True):
         """``set_to_none=True`` (torch's default) drops the gradients as torch does; ``False`` zeroes every gradient in place in one
@@ -289,28 +301,251 @@ class FullModelClipAdamW(torch.optim.Optimizer):
             if self._n_tensors:
                 ops.optim_zero(self._rec_dev, self._chk_dev, self._n_tensors, self._n_chunks)
 
+    def _counts(self):
+        """Steps taken per parameter; device counts are read back here (a wait: state_dict() may, step() may not)."""
+        if self._device_counts:
+            return self._steps_dev.cpu().tolist()
+        return [self._calls - o for o in self._off]
+
     def state_dict(self):
-        """torch's layout; ``step`` of every parameter is materialised here from the call count (a float32 scalar, as torch keeps it)."""
-        if self._params is not None:
-            for i, p in enumerate(self._params):
-                if p in self.state and "exp_avg" in self.state[p]:
-                    self.state[p]["step"] = torch.tensor(float(self._calls - self._off[i]))
-        return super().state_dict()
+        """torch's layout; the step counts are materialised here (``step`` a float32 scalar, as torch keeps it).  With the counts on
+        the device a parameter that has not stepped -- every step since its state was made was skipped -- is written out as torch
+        would have it: without state."""
+        if self._params is None:
+            return super().state_dict()
+        counts = self._counts()
+        self._write_counts(counts)
+        sd = super().state_dict()
+        if self._device_counts:
+            for i, n in enumerate(counts):
+                if n == 0:
+                    sd["state"].pop(i, None)
+        return sd
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         if self._params is None:
             with torch.cuda.device(self._first_device()):
                 self._layout()
-        for i, p in enumerate(self._params):
-            st = self.state.get(p)
-            self._off[i] = self._calls - (int(st["step"]) if st and "step" in st else 0)
+        counts = self._loaded_counts()
+        if self._device_counts:
+            self._upload_counts(counts)
+        else:
+            self._off = [self._calls - n for n in counts]
         self._hyper_key = self._table_key = None         # new state tensors, new offsets: the next step uploads the table
 
 
+class _AdamFamily(_TableOptimizer):
+    """State ``step``, ``exp_avg``, ``exp_avg_sq`` per parameter and the hyper-parameters of torch.optim.Adam / AdamW."""
+
+    _hyper_of = staticmethod(_HYPER)
+
+    def _check_args(self, lr, betas, eps, weight_decay, amsgrad, maximize):
+        if amsgrad:
+            raise NotImplementedError(f"{self._NAME}: amsgrad=True is not supported")
+        if maximize:
+            raise NotImplementedError(f"{self._NAME}: maximize=True is not supported")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+
+    def _group_rows(self, key):
+        for gi, (lr, wd, betas, eps, amsgrad, maximize) in enumerate(key):
+            if amsgrad or maximize:
+                raise NotImplementedError(f"{self._NAME}: param group {gi} sets {'amsgrad' if amsgrad else 'maximize'}")
+            if isinstance(lr, torch.Tensor) or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+                raise ValueError(f"{self._NAME}: param group {gi}: lr must be a Python float and betas in [0, 1), got "
+                                 f"{type(lr).__name__}, {betas}")
+        return np.array([(lr, wd, betas[0], betas[1], eps, 0.0, 0.0, 0.0) for lr, wd, betas, eps, _, _ in key], dtype=np.float64)
+
+    def _state_of(self, i, p):
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            self._off[i] = self._calls
+        m, v = st["exp_avg"], st["exp_avg_sq"]
+        self._check_state(i, p, (("exp_avg", m), ("exp_avg_sq", v)))
+        return m, v
+
+    def _write_counts(self, counts):
+        for p, n in zip(self._params, counts):
+            if p in self.state and "exp_avg" in self.state[p]:
+                self.state[p]["step"] = torch.tensor(float(n))
+
+    def _loaded_counts(self):
+        states = [self.state.get(p) for p in self._params]
+        return [int(st["step"]) if st and "step" in st else 0 for st in states]
+
+
+class FullModelClipAdamW(_AdamFamily):
+    """``torch.optim.AdamW`` behind ``torch.nn.utils.clip_grad_norm_(all parameters, max_norm)``, two launches per ``step()``.
+
+    ``params``, ``lr``, ``betas``, ``eps``, ``weight_decay`` and ``param_groups`` are torch's: a scheduler that writes
+    ``group["lr"]`` works unchanged, and ``state_dict()`` / ``load_state_dict()`` are interchangeable with ``torch.optim.AdamW`` over
+    the same groups (per parameter ``step``, ``exp_avg``, ``exp_avg_sq``).  ``max_norm <= 0`` turns the clipping off.  A parameter
+    whose ``.grad`` is None is left out of the step as torch leaves it out: no norm contribution, no state change, no step count.
+
+    The host keeps what it last uploaded -- the hyper-parameters of every group and the addresses of every parameter and
+    gradient -- and uploads again, in one asynchronous copy from pinned staging, only when one of them changed: a scheduler's lr
+    (the 64-byte rows alone), a gradient reallocated after ``zero_grad(set_to_none=True)`` or a parameter without a gradient (the
+    whole table).  ``uploads`` counts the copies.  ``step()`` copies nothing back, never synchronises and allocates nothing after
+    the first call with a given set of gradients; ``zero_grad(set_to_none=False)`` is one launch over the same table.
+    ``last_grad_norm`` / ``last_clip_coef``: 0-d float32 device tensors (views of the kernels' state block) of the last step, the
+    norm before clipping; None before the first step, and with ``max_norm <= 0`` the norm is not computed and reads 0.
+    Everything is issued on the stream that is current when ``step()`` is called; use one stream for the steps of one optimizer.
+
+    Under a ``torch.amp.GradScaler`` (``scaler.step(optimizer)``) the kernels unscale the gradients and skip the step when the
+    scaler found an inf: no parameter, state or step count changes, ``last_grad_norm`` / ``last_clip_coef`` keep the last taken
+    step's values, and ``.grad`` stays scaled (the reference's ``unscale_`` has divided it by then; nothing reads it before
+    ``zero_grad``).  After a taken step ``.grad`` holds the unscaled, clipped gradient.  From the first step that meets a scaler
+    the step counts live on the device (uploaded once from the host's) and ``state_dict()`` reads them back.
+
+    Not supported (NotImplementedError): ``amsgrad``, ``maximize``, a ``closure``, parameters other than float32;
+    RuntimeError: host tensors, non-contiguous parameters or gradients, parameters on several devices."""
+
+    _NAME = "FullModelClipAdamW"
+    _RULE = "adamw"
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 max_norm=0.01):
+        self._check_args(lr, betas, eps, weight_decay, amsgrad, maximize)
+        # the keys of torch.optim.AdamW's own groups, so that a state dict of either loads into the other and then steps
+        defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)
+        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
+        self._setup(max_norm, device_counts=False)
+        super().__init__(params, defaults)
+
+
+class Adam(_AdamFamily):
+    """``torch.optim.Adam`` (no amsgrad: weight decay added to the gradient, bias-corrected moments) in two launches per ``step()``,
+    behind ``clip_grad_norm_`` over all parameters when ``max_norm > 0`` (off by default, as in tools/train_net.py:136-138).
+
+    Param groups of any number of tensors; everything else as ``FullModelClipAdamW``: torch's ``param_groups``, schedulers write
+    ``group["lr"]``, ``state_dict()`` / ``load_state_dict()`` interchangeable with ``torch.optim.Adam`` (``step``, ``exp_avg``,
+    ``exp_avg_sq``; ``state_dict()`` reads the step counts from the device and may wait, ``step()`` never does), ``uploads``,
+    ``last_grad_norm`` / ``last_clip_coef``, ``zero_grad(set_to_none=False)`` in one launch, GradScaler's fused protocol.
+
+    Not supported (NotImplementedError): ``amsgrad``, ``maximize``, a ``closure``, parameters other than float32;
+    RuntimeError: host tensors, non-contiguous parameters or gradients, parameters on several devices."""
+
+    _NAME = "Adam"
+    _RULE = "adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, max_norm=0.0):
+        self._check_args(lr, betas, eps, weight_decay, amsgrad, maximize)
+        defaults = dict(torch.optim.Adam([torch.zeros(1)]).defaults)
+        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
+        self._setup(max_norm, device_counts=True)
+        super().__init__(params, defaults)
+
+
+class SGD(_TableOptimizer):
+    """``torch.optim.SGD`` (momentum, dampening, nesterov, weight decay added to the gradient) in two launches per ``step()``, behind
+    ``clip_grad_norm_`` over all parameters when ``max_norm > 0`` (the "SGD" branch of Trainer.build_optimizer clips, the UCN
+    trainer does not).
+
+    State per parameter is ``momentum_buffer`` alone, as in torch, and only with momentum != 0; whether a tensor has stepped -- its
+    first step sets the buffer to the gradient, undampened -- is counted on the device.  ``state_dict()`` / ``load_state_dict()``
+    are interchangeable with ``torch.optim.SGD``: a loaded buffer means "has stepped", a tensor that has not stepped is written out
+    without one.  A group whose momentum goes from 0 to non-zero in mid-run gets fresh buffers, and its tensors count from there.  Everything else as ``FullModelClipAdamW``: param groups of any number of tensors, schedulers write
+    ``group["lr"]``, ``uploads``, ``last_grad_norm`` / ``last_clip_coef``, ``zero_grad(set_to_none=False)`` in one launch,
+    GradScaler's fused protocol; ``step()`` never waits, ``state_dict()`` may.
+
+    Not supported (NotImplementedError): ``maximize``, a ``closure``, parameters other than float32;
+    RuntimeError: host tensors, non-contiguous parameters or gradients, parameters on several devices."""
+
+    _NAME = "SGD"
+    _RULE = "sgd"
+    _hyper_of = staticmethod(_SGD_HYPER)
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, max_norm=0.0):
+        if maximize:
+            raise NotImplementedError("SGD: maximize=True is not supported")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(torch.optim.SGD([torch.zeros(1)], lr=1e-3).defaults)
+        defaults.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False)
+        self._setup(max_norm, device_counts=True)
+        super().__init__(params, defaults)
+
+    def _group_rows(self, key):
+        for gi, (lr, wd, momentum, dampening, nesterov, maximize) in enumerate(key):
+            if maximize:
+                raise NotImplementedError(f"SGD: param group {gi} sets maximize")
+            if isinstance(lr, torch.Tensor) or momentum < 0.0:
+                raise ValueError(f"SGD: param group {gi}: lr must be a Python float and momentum >= 0, got {type(lr).__name__}, "
+                                 f"{momentum}")
+            if nesterov and (momentum <= 0 or dampening != 0):
+                raise ValueError(f"SGD: param group {gi}: Nesterov momentum requires a momentum and zero dampening")
+        return np.array([(lr, wd, 0.0, 0.0, 0.0, momentum, dampening, 1.0 if nesterov else 0.0) for lr, wd, momentum, dampening,
+                         nesterov, _ in key], dtype=np.float64)
+
+    def _table_extra(self):
+        return tuple(g["momentum"] != 0 for g in self.param_groups)      # a group that starts to keep a buffer: new records
+
+    def _state_of(self, i, p):
+        if self.param_groups[self._group_of[i]]["momentum"] == 0:
+            return None, None
+        st = self.state[p]
+        if st.get("momentum_buffer") is None:
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            if i in self._seen:         # stepped without a buffer (its group's momentum was 0 until now): torch's buffer is None
+                self._steps_dev[i:i + 1].fill_(0)       # there, so the next step is its first -- buf = d, undampened
+        buf = st["momentum_buffer"]
+        self._check_state(i, p, (("momentum_buffer", buf),))
+        return buf, None
+
+    def _write_counts(self, counts):
+        pass                                # no step key in torch.optim.SGD's state
+
+    def _loaded_counts(self):
+        states = [self.state.get(p) for p in self._params]
+        return [1 if st and st.get("momentum_buffer") is not None else 0 for st in states]
+
+
+def build_ucn_param_groups(network, weight_decay=1e-4):
+    """The two param groups of the UCN embedding network's trainer (tools/train_net.py:133-134 over SEGNET.bias_parameters() /
+    weight_parameters(), lib/networks/SEG.py:122-126): every parameter whose name holds 'bias', then every one whose name holds
+    'weight', in the order of ``named_parameters()``, both at TRAIN.WEIGHT_DECAY (1e-4, lib/fcn/config.py).  Host only."""
+    named = list(network.named_parameters())
+    return [{"params": [p for n, p in named if "bias" in n], "weight_decay": weight_decay},
+            {"params": [p for n, p in named if "weight" in n], "weight_decay": weight_decay}]
+
+
+def build_ucn_optimizer(network, solver="sgd", lr=1e-4, momentum=0.9, beta=0.999, weight_decay=1e-4):
+    """The optimizer tools/train_net.py:130-142 builds over ``build_ucn_param_groups(network)``: ``solver`` "sgd" (its default:
+    ``SGD(momentum=TRAIN.MOMENTUM)``, driven by a MultiStepLR) or "adam" (``Adam(betas=(TRAIN.MOMENTUM, TRAIN.BETA))``); defaults
+    TRAIN.LEARNING_RATE 1e-4, MOMENTUM 0.9, BETA 0.999, WEIGHT_DECAY 1e-4.  Neither clips."""
+    if solver not in ("sgd", "adam"):
+        raise ValueError(f"build_ucn_optimizer: solver must be 'sgd' or 'adam', got {solver!r}")
+    groups = build_ucn_param_groups(network, weight_decay)
+    if solver == "sgd":
+        return SGD(groups, lr, momentum=momentum)
+    return Adam(groups, lr, betas=(momentum, beta))
+
+
 def build_optimizer(model, base_lr=1e-4, weight_decay=0.05, weight_decay_norm=0.0, weight_decay_embed=0.0, backbone_multiplier=0.1,
-                    betas=(0.9, 0.999), eps=1e-8, max_norm=0.01):
+                    betas=(0.9, 0.999), eps=1e-8, max_norm=0.01, optimizer="ADAMW", momentum=0.9):
     """The optimizer every shipped config trains with (OPTIMIZER "ADAMW", CLIP_TYPE "full_model", CLIP_VALUE 0.01):
-    ``FullModelClipAdamW(build_param_groups(model, ...), lr=base_lr, max_norm=max_norm)``."""
+    ``FullModelClipAdamW(build_param_groups(model, ...), lr=base_lr, max_norm=max_norm)``.  ``optimizer="SGD"`` is the reference's
+    other branch (:179-182): ``SGD(the same groups, lr=base_lr, momentum=momentum)`` (SOLVER.MOMENTUM 0.9) behind the same
+    clipping.  Anything else raises NotImplementedError, as the reference does."""
     groups = build_param_groups(model, base_lr, weight_decay, weight_decay_norm, weight_decay_embed, backbone_multiplier)
+    if optimizer == "SGD":
+        return SGD(groups, lr=base_lr, momentum=momentum, max_norm=max_norm)
+    if optimizer != "ADAMW":
+        raise NotImplementedError(f"no optimizer type {optimizer}")
     return FullModelClipAdamW(groups, lr=base_lr, betas=betas, eps=eps, max_norm=max_norm)

@@ -627,3 +627,14 @@ def ucn_model_losses(model, image, depth, targets, criterion, *, labels=None, em
         raise ValueError("ucn_model_losses: embedding_loss needs labels and embedding_weight")
     norm = ucn_backbone_forward_train(model.backbone, image, depth if model.use_depth else None, renormalize=True)
     return _head_losses_normalised(model.sem_seg_head, norm, targets, criterion, labels, embedding_loss, embedding_weight)
+
+
+def ucn_embedding_losses(network, image, label, depth=None, *, embedding_loss):
+    """The training branch of the UCN embedding network (SEGNET.forward lib/networks/SEG.py:88-120 with its embedding loss, as
+    train_segnet calls it, lib/fcn/train.py:57) for ``network`` = ucn_backbone.UCNBackbone and ``embedding_loss`` =
+    embedding_loss.EmbeddingLoss: image (B, 3, H, W), label (B, 1, H, W) cluster ids, depth (B, 3, H, W) xyz or None ->
+    (loss, intra_cluster_loss, inter_cluster_loss, features), features (B, num_units, H, W) under autograd
+    (ucn_backbone_forward_train).  ``loss.backward()`` reaches every parameter of the towers that ran."""
+    features = ucn_backbone_forward_train(network, image, depth)
+    loss, intra, inter = embedding_loss(features, label)
+    return loss, intra, inter, features
