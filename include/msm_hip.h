@@ -82,7 +82,7 @@ extern "C" {
 #define MSM_E_WORKSPACE (-3) /* workspace too small */
 
 const char* msm_last_error_string(void);
-#define MSM_ABI_VERSION 43   /* 43: msm_optim_count_norm / msm_optim_update, MSM_OPTIM_ADAMW / _ADAM / _SGD (AdamW, Adam and SGD over the optimizer's table with per-tensor step counts on the device, the gradient unscaled and the step skipped inside the launches: GradScaler's grad_scale / found_inf); 42: msm_crop_boxes / msm_train_crop (the SYN_CROP training path on the device: one object box per frame, squared and padded, then colour, label and xyz cropped there and resized to S x S in one launch); 41: msm_augment_color / msm_augment_depth + msm_augment_depth_workspace / msm_xyz_noise, msm_augment_table_row (the training loader's random augmentations of a batch on the device: HLS shift, pixel noise, motion blur, depth scaling and ellipse dropout, point-cloud noise); 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_grad_norm / msm_optim_adamw_step / msm_optim_zero + msm_optim_chunk (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
+#define MSM_ABI_VERSION 44   /* 44: the host-counted AdamW entry pair of 37 removed (AdamW steps through msm_optim_count_norm / msm_optim_update like Adam and SGD, its three fma forms part of the definition; state[0] of the optimizer's state block is reserved); 43: msm_optim_count_norm / msm_optim_update, MSM_OPTIM_ADAMW / _ADAM / _SGD (AdamW, Adam and SGD over the optimizer's table with per-tensor step counts on the device, the gradient unscaled and the step skipped inside the launches: GradScaler's grad_scale / found_inf); 42: msm_crop_boxes / msm_train_crop (the SYN_CROP training path on the device: one object box per frame, squared and padded, then colour, label and xyz cropped there and resized to S x S in one launch); 41: msm_augment_color / msm_augment_depth + msm_augment_depth_workspace / msm_xyz_noise, msm_augment_table_row (the training loader's random augmentations of a batch on the device: HLS shift, pixel noise, motion blur, depth scaling and ellipse dropout, point-cloud noise); 40: msm_msdeform_attn_bwd_det + msm_msdeform_attn_bwd_det_workspace (deterministic MSDeformAttn backward: per-destination 64-bit fixed point); 39: msm_target_tables / msm_target_write / msm_sample_labels + msm_sample_labels_workspace, msm_target_table_row (training targets from instance label images: masks, boxes, dense and sampled label maps of a batch on the device), msm_point_loss_bwd accumulates masks up to 20 479 pixels in fixed point (bit-reproducible gradients); 38: msm_ucn_embedding_tail_bwd + msm_ucn_embedding_tail_bwd_workspace (backward of the UCN embedding tail: training the RGB-D backbone from images); 37: msm_optim_zero + msm_optim_chunk and a host-counted norm / AdamW-step entry pair, removed in 44 (full-model-clipped AdamW over a device-resident table of tensors: the reference's optimizer in two launches); 36: msm_groupnorm_bwd_f32 + msm_groupnorm_bwd_workspace, msm_upsample_bilinear_tokens_f32 / _bwd_tokens_f32 (GroupNorm and FPN-upsampling backward: training the ResNet-50 pixel decoder); 35: msm_conv3x3_c64_wgrad + msm_conv3x3_c64_wgrad_workspace (weight and bias gradient of the 3x3 mask_features convolution: training the RGB-D head); 34: msm_embloss_fwd / _bwd / _workspace (EmbeddingLoss, the UCN clustering loss, forward and backward on per-cluster sums); 33: msm_lsap_match (the criterion's assignments solved on the device: pairs, target classes and a status per problem); 31: msm_prepare_inputs (input normalisation and the zero padding to the size divisibility of an image / depth batch in one launch); 30: one msm_ms_* entry per clustering stage with an M (maps) argument: the msm_ms_*_batched entries of 28 took the plain names, one map is M = 1 (msm_ms_select_seeds: device first_indices or a host first_index; msm_ms_seed_workspace(M, n)); 29: msm_groupnorm_nchw_pool_f32 (the 64-channel activation as NCHW planes and its pooled centre-tap maps from one pass), MSM_OPT_GN_POOL, MSM_OPT_MASK_KERNEL = 7; 28: msm_ms_*_batched (the classic clustering for M maps of one size per call: grouped persistent seeding, hill climb, merge, assignment and relabel with a map dimension); 27: msm_mask_nms + msm_mask_nms_workspace (mask NMS of a batch of images on bit planes: label image, score image, boxes); 26: msm_ingest_frames (raw BGR8 + depth camera frames -> the image and xyz tensors, border padding included); 25: msm_instance_postprocess_resized (instance masks at a requested output size: upsample, crop and resize in one pass), MSM_OPT_POST_RESIZE_DIRECT; 24: msm_match_cost, msm_point_loss_fwd / _bwd / _workspace (the set criterion: matching costs and point-sampled mask losses); 23: msm_eval_counts + msm_eval_counts_workspace (the integer counts of multilabel_metrics); 22: msm_groupnorm_apply_f16 + msm_conv3x3_c64_f16h (the f16 plan's FPN level on a half token map), msm_conv1x1_in_multi_wide; 21: msm_dec_heads_mask (the next layer's attention mask as the heads kernel's epilogue), msm_l2_prefetch / msm_dec_set_prefetch, msm_dec_*_bf16x2 (hi + lo weight fragments), MSM_OPT_DEC_TILE32; 20: msm_ucn_embedding_tail; 19: backbone glue (msm_bias_act_nhwc, msm_nhwc_to_nchw_f32); 18: flags argument of msm_attn_mask_pooled (bit 1: IEEE-half operands); 17: msm_f32_to_f16_rows; 16: msm_mask_conv3x3_folded (the UCN mask step with the 3x3 mask_features convolution folded into the query embedding); 15: IEEE-half operand forms of the 16-bit plan (precision "f16": msm_dec_*_f16, msm_encoder_block_hm_fwd ffn_f16, fp16 keys in the low-precision attention); 14: cmat_width argument of the K/V projections (separable position constants), msm_conv3x3_c64_nchw_bf16, msm_encoder_prologue_hm_fwd; 13: flags argument of msm_ms_select_seeds_bf16 (persistent on-chip seeding over the bf16 copy), input projections on the bf16 matrix pipe (msm_conv1x1_in_lp, msm_conv1x1_in_multi_lp); 12: head-major bf16 activations between the encoder kernels of the bf16 plan (msm_encoder_block_hm_fwd, msm_msdeform_attn_enc_lp_fwd, msm_f32_to_f16); 11: mean-shift hill climb and the 3x3 FPN convolution with fp32 results on the bf16 matrix pipe (msm_ms_hill_climb_split, msm_groupnorm_apply_split + msm_conv3x3_c64_split), msm_topk_class_scores_gather, zero_buf arguments of msm_pool_mask_taps; 10: bf16-operand 3x3 convolution (msm_conv3x3_c64_bf16), attention masks at key resolution (msm_pool_mask_taps, msm_attn_mask_pooled); 9: float64 MSDeformAttn entry points (_f64), any channel count; 8: bf16 decoder tails, low-precision attention, bf16 K/V projection, split-fp32 encoder block; 7: msm_set_option replaces the environment switches; fused K/V attention, bf16 and backward entry points; 6: post-process workspace size; 5: embed stride / per-query bias of the mask step; 2: flags argument of the mask step, head-major value / packed-weight entry points; 3: msm_label_stats; 4: padded-frame post-process, GroupNorm moment / stride arguments, input-projection, prologue, 3x3 and batched K/V entry points */
 int msm_abi_version(void);
 
 /* Kernel-selection overrides for tools/ and tests/ (NOT read on the product path: every option defaults to
@@ -1267,82 +1267,77 @@ int msm_embloss_bwd(const float* x, const float* labels, const float* grad_losse
                     int64_t workspace_bytes, float* grad_x, int B, int C, int HW, int max_clusters, int metric, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Full-model-clipped AdamW (Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191): torch.nn.utils.
- * clip_grad_norm_(all parameters, max_norm) followed by torch.optim.AdamW, for any number of tensors in two launches over a
- * device-resident table that the caller writes.
- *   tensors  [n_tensors][8] int64, one record per tensor: the device addresses of p, g (the gradient), exp_avg and exp_avg_sq (fp32,
- *            contiguous, numel elements each, 4-byte aligned), numel (>= 1), the index of its hyper-parameter row, flags
- *            (MSM_OPTIM_ALIGNED: all four addresses are 16-byte aligned; MSM_OPTIM_ALIGNED_G: g is), 0
- *   chunks   [n_chunks][2] int64 (tensor, offset): every tensor cut into ceil(numel / MSM_OPTIM_CHUNK) chunks at offsets 0,
- *            MSM_OPTIM_CHUNK, 2 MSM_OPTIM_CHUNK, ... (multiples of 4 elements), in any order; a launch is one workgroup per chunk, so a
- *            3-element bias and a 524 288-element weight are balanced work.  MSM_OPTIM_CHUNK = 8192 elements (32 KiB per
- *            stream); msm_optim_chunk() returns it.  A pair that points outside the table is skipped.
- *   hyper    [n_rows][8] double: lr, weight_decay, beta1, beta2, eps, step offset (an integer), 0, 0
- *   partials [n_chunks] double (scratch: written by msm_optim_grad_norm, read by msm_optim_adamw_step)
- *   state    [2] int64: [0] the call counter; the 8 bytes of [1] hold two fp32, total_norm then coef, left by the last step
- *            (zero-initialised by the caller before the first call)
- * msm_optim_grad_norm: partials[c] = sum of g^2 over chunk c, accumulated in double, and state[0] += 1.  16-byte loads where the
- * flag says g is aligned, a scalar path for other tensors and for the last numel % 4 elements.
- * msm_optim_adamw_step: every workgroup adds the partials in one fixed order (so all form the same bits), total_norm = sqrt(sum),
- * coef = min(1, max_norm / (total_norm + 1e-6)) in double -- clip_grad_norm_'s expressions -- and applies torch's AdamW to its chunk
- * in fp32 with step = state[0] - step offset and the scalars of the tensor's row prepared in double (bc_i = 1 - beta_i^step):
- *     g <- g coef (written back when coef != 1: the reference clips .grad in place);   p <- p (1 - lr wd);
- *     m <- m + (1 - beta1) (g - m);   v <- beta2 v + (1 - beta2) g^2;   p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
- * With max_norm > 0 it must follow msm_optim_grad_norm of the same table on the same stream (that launch advanced the counter);
- * with max_norm <= 0 nothing is clipped (coef = 1, total_norm = 0, g is not written, partials may be null) and the call advances
- * the counter itself in a launch of its own, so the counter is never written by the kernel that reads it.  One step is therefore
- * one increment: a tensor whose first step is the call that makes the counter k has step offset k - 1.
- * msm_optim_zero: g = 0 for every chunk of the table (zero_grad(set_to_none=False) in one launch; hyper and state are not read).
- * No atomics and no hand-off between workgroups: results repeat bit for bit for a given table.  n_tensors >= 1, n_chunks >=
- * n_tensors, n_rows >= 1, tables 8-byte aligned, else MSM_E_INVALID. */
-#define MSM_OPTIM_CHUNK 8192
-#define MSM_OPTIM_ALIGNED 1
-#define MSM_OPTIM_ALIGNED_G 2
-int msm_optim_chunk(void);
-int msm_optim_grad_norm(const int64_t* tensors, const int64_t* chunks, double* partials, int64_t* state, int n_tensors,
-                        int n_chunks, void* stream);
-int msm_optim_adamw_step(const int64_t* tensors, const int64_t* chunks, const double* hyper, const double* partials,
-                         int64_t* state, int n_tensors, int n_chunks, int n_rows, float max_norm, void* stream);
-int msm_optim_zero(const int64_t* tensors, const int64_t* chunks, int n_tensors, int n_chunks, void* stream);
-
-/* AdamW, Adam and SGD over the same table with the step counts on the device and GradScaler's fused protocol inside the launches
- * (torch.optim.Adam / SGD: tools/train_net.py:130-142 and the "SGD" branch of Trainer.build_optimizer :179-182; grad_scale /
- * found_inf: torch/amp/grad_scaler.py:403-454, the step of AMPTrainer.run_step :209-246).  tensors, chunks, partials and state [1]
- * as above; state[0] is not touched.  What differs:
+ * The optimizers: torch.nn.utils.clip_grad_norm_(all parameters, max_norm) followed by torch.optim.AdamW, Adam or SGD, for any
+ * number of tensors in two launches over a device-resident table that the caller writes, with the step counts on the device and
+ * GradScaler's fused protocol inside the launches.  (AdamW with one param group per tensor: Trainer.build_optimizer, MSMFormer/
+ * tabletop_train_net_pretrained.py:113-191, "SGD" its other branch :179-182; Adam / SGD: tools/train_net.py:130-142; grad_scale /
+ * found_inf: torch/amp/grad_scaler.py:403-454, the step of AMPTrainer.run_step :209-246.)
  *   rule       MSM_OPTIM_ADAMW, MSM_OPTIM_ADAM or MSM_OPTIM_SGD, one for the whole table
- *   tensors    the row field of a record also indexes steps: every record of a table has a row of its own.  exp_avg is SGD's
- *              momentum_buffer; an address the rule does not read is 0 (SGD: exp_avg_sq always, exp_avg with momentum 0) and counts
- *              as aligned for MSM_OPTIM_ALIGNED.  A record without an address its rule reads is skipped.
+ *   tensors    [n_tensors][8] int64, one record per tensor: the device addresses of p, g (the gradient), exp_avg (SGD: momentum_buffer)
+ *              and exp_avg_sq (fp32, contiguous, numel elements each, 4-byte aligned), numel (>= 1), its row (of hyper and of steps:
+ *              every record of a table has a row of its own), flags (MSM_OPTIM_ALIGNED: all four addresses are 16-byte aligned;
+ *              MSM_OPTIM_ALIGNED_G: g is), 0.  An address the rule does not read is 0 (SGD: exp_avg_sq always, exp_avg with momentum
+ *              0) and counts as aligned for MSM_OPTIM_ALIGNED.  A record without an address its rule reads is skipped.
+ *   chunks     [n_chunks][2] int64 (tensor, offset): every tensor cut into ceil(numel / MSM_OPTIM_CHUNK) chunks at offsets 0,
+ *              MSM_OPTIM_CHUNK, 2 MSM_OPTIM_CHUNK, ... (multiples of 4 elements), in any order; a launch is one workgroup per chunk, so
+ *              a 3-element bias and a 524 288-element weight are balanced work.  MSM_OPTIM_CHUNK = 8192 elements (32 KiB per
+ *              stream); msm_optim_chunk() returns it.  A pair that points outside the table is skipped.
  *   hyper      [n_rows][8] double: lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov (0 or 1); the three Adam
- *              columns are not read by SGD, the three SGD columns not by AdamW and Adam (there is no step offset: steps has it)
+ *              columns are not read by SGD, the three SGD columns not by AdamW and Adam
+ *   partials   [n_chunks] double (scratch: written by msm_optim_count_norm, read by msm_optim_update)
+ *   state      [2] int64, zero-initialised by the caller: [0] is reserved, neither read nor written; the 8 bytes of [1] hold two
+ *              fp32, total_norm then coef, left by the last step that was taken
  *   steps      [n_rows] int64: the steps taken by the tensor of that row, 0 for one that never stepped (zero-initialised or
  *              uploaded by the caller).  Advanced by one for exactly the records of the table, and only when the step is taken.
  *   grad_scale one fp32 on the device or null: g' = g (float)(1.0 / (double)*grad_scale), exact for a power of two; null: g' = g
  *   found_inf  one fp32 on the device or null: *found_inf != 0 (a nan too) skips the step -- p, exp_avg, exp_avg_sq, steps, g
  *              and state stay bit for bit as they are (partials is scratch and is written)
- * msm_optim_count_norm: partials[c] = sum of g'^2 over chunk c in double; the workgroup of the chunk at offset 0 of a tensor
- * advances its count unless the step is skipped.  msm_optim_update: total_norm and coef from the partials as msm_optim_adamw_step
- * forms them (max_norm <= 0: coef = 1, total_norm = 0, partials may be null, and the counts are advanced by a launch of its own in
- * front of the update, one thread per record), then per chunk, scalars prepared once per workgroup in double, elements in fp32,
- * with step = steps[row] as the launch in front left it (a count is never written by the kernel that reads it):
+ * msm_optim_count_norm: partials[c] = sum of g'^2 over chunk c, accumulated in double; the workgroup of the chunk at offset 0 of a
+ * tensor advances its count unless the step is skipped.  16-byte loads where the flag says g is aligned, a scalar path for other
+ * tensors and for the last numel % 4 elements.
+ * msm_optim_update: every workgroup adds the partials in one fixed order (so all form the same bits), total_norm = sqrt(sum),
+ * coef = min(1, max_norm / (total_norm + 1e-6)) in double -- clip_grad_norm_'s expressions.  With max_norm <= 0 nothing is clipped
+ * (coef = 1, total_norm = 0, partials may be null) and the counts are advanced by a launch of its own in front of the update, one
+ * thread per record.  Then per chunk, the scalars of the tensor's row prepared once per workgroup in double (bc_i = 1 -
+ * beta_i^step), elements in fp32, with step = steps[row] as the launch in front left it (a count is never written by the kernel
+ * that reads it):
  *     g' <- g' coef;  g <- g' (written back when grad_scale is given or coef != 1: unscale_ and clip_grad_norm_ work in place)
- *   MSM_OPTIM_ADAMW  the arithmetic of msm_optim_adamw_step operation for operation: with grad_scale and found_inf null the same
- *                    bits for the same table and step
+ *   MSM_OPTIM_ADAMW  p <- p (1 - lr wd);  m <- m + (1 - beta1) (g' - m);  v <- beta2 v + (1 - beta2) g'^2;
+ *                    p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)            (torch.optim.AdamW, no amsgrad)
+ *                    Which of these products are fused into an fma is part of the definition, per access path, and the bits that
+ *                    follow are held by a recorded fixture (tests/golden/optim_adamw_bits.json).  With d = g' - m, gg = (1 - beta2) g',
+ *                    vb = v beta2, q = (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)) and every other operation rounded on its own:
+ *                      a tensor without MSM_OPTIM_ALIGNED (scalar accesses): no fma --
+ *                                m <- m + d (1 - beta1);  v <- vb + gg g';  p <- p (1 - lr wd) - q
+ *                      16-byte accesses: m, v and p fused --
+ *                                m <- fma(1 - beta1, d, m);  v <- fma(g', gg, vb);  p <- fma(1 - lr wd, p, -q)
+ *                      the last numel % 4 elements of an aligned tensor: m alone fused --
+ *                                m <- fma(1 - beta1, d, m);  v <- vb + gg g';  p <- p (1 - lr wd) - q
  *   MSM_OPTIM_ADAM   d = g' + wd p (wd != 0; not written back);  m <- m + (1 - beta1) (d - m);  v <- beta2 v + (1 - beta2) d^2;
  *                    p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)            (torch.optim.Adam, no amsgrad)
  *   MSM_OPTIM_SGD    d = g' + wd p (wd != 0; not written back);  with momentum != 0: buf <- d on the tensor's first taken step
  *                    (step == 1, undampened as in torch), else buf <- momentum buf + (1 - dampening) d;  d <- d + momentum buf
  *                    with nesterov, else d <- buf;  p <- p - lr d                   (torch.optim.SGD)
+ *                    Adam and SGD: every operation rounded on its own on every path, no fma.
  * With max_norm > 0 msm_optim_update must follow msm_optim_count_norm of the same table, grad_scale and found_inf on the same
- * stream.  No atomics, no hand-off between workgroups; same argument checks as above, grad_scale / found_inf 4-byte aligned. */
+ * stream.
+ * msm_optim_zero: g = 0 for every chunk of the table (zero_grad(set_to_none=False) in one launch; hyper, state and steps are not
+ * read).
+ * No atomics and no hand-off between workgroups: results repeat bit for bit for a given table.  n_tensors >= 1, n_chunks >=
+ * n_tensors, n_rows >= 1, tables 8-byte aligned, grad_scale / found_inf 4-byte aligned, else MSM_E_INVALID. */
+#define MSM_OPTIM_CHUNK 8192
+#define MSM_OPTIM_ALIGNED 1
+#define MSM_OPTIM_ALIGNED_G 2
 #define MSM_OPTIM_ADAMW 0
 #define MSM_OPTIM_ADAM 1
 #define MSM_OPTIM_SGD 2
+int msm_optim_chunk(void);
 int msm_optim_count_norm(const int64_t* tensors, const int64_t* chunks, double* partials, int64_t* steps, const float* grad_scale,
                          const float* found_inf, int n_tensors, int n_chunks, int n_rows, void* stream);
 int msm_optim_update(int rule, const int64_t* tensors, const int64_t* chunks, const double* hyper, const double* partials,
                      int64_t* state, int64_t* steps, const float* grad_scale, const float* found_inf, int n_tensors, int n_chunks,
                      int n_rows, float max_norm, void* stream);
+int msm_optim_zero(const int64_t* tensors, const int64_t* chunks, int n_tensors, int n_chunks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training targets from instance label images: what the reference builds per image on the host and uploads as T dense masks

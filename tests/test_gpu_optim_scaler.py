@@ -2,14 +2,22 @@
 optimizer and calls ``step()``) in optim.FullModelClipAdamW, optim.Adam and optim.SGD: the kernels unscale the gradient, skip the step on
 found_inf and count the steps of every tensor on the device; nothing waits for the GPU.
 
-Bits are compared where two runs of the same kernels must agree (a power-of-two scale is exact, a skipped step changes nothing, the
-device-counted AdamW is the host-counted one); the float64 references of tests/optim_cases.py / tests/optim_rule_cases.py are held to
+Bits are compared where two runs of the same kernels must agree (a power-of-two scale is exact, a skipped step changes nothing) and
+where AdamW must stay what it was (the recorded fixture tests/golden/optim_adamw_bits.json); the float64 references of tests/optim_cases.py / tests/optim_rule_cases.py are held to
 their contract, max|got - ref64| <= 1e-4 max|ref64| per tensor.  Needs a real MI355X (pytest -m gpu)."""
+import json
+import math
+import os
+import sys
+
 import pytest
 import torch
 
 import optim_cases as OC
 import optim_rule_cases as RC
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import record_optim_bits as RB  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -83,27 +91,93 @@ def _scalars(opt, scale, found):
     opt.found_inf = torch.full((), found, dtype=torch.float32, device=DEV)
 
 
-def test_device_counted_adamw_is_the_host_counted_one():
-    tensors, case, make, groups, keys, _ = _setup("adamw", "clip_active")
-    _, opt_a, host = _trace(tensors, case, make, groups, keys, (1, 2, 3))
-    _, opt_b, dev = _trace(tensors, case, make, groups, keys, (1, 2, 3), pre_step=lambda i, params, opt: _scalars(opt, 1.0, 0.0))
-    assert not opt_a._device_counts and opt_b._device_counts
-    for step, (a, b) in enumerate(zip(host, dev), 1):
-        _same(a, b, f"step {step}")
-    sd_a, sd_b = opt_a.state_dict()["state"], opt_b.state_dict()["state"]
-    steps = [float(sd_b[i]["step"]) for i in range(len(tensors))]
-    assert steps == [float(sd_a[i]["step"]) for i in range(len(tensors))] == [2.0 if t.name == "skip" else 3.0 for t in tensors]
+def test_adamw_reproduces_the_recorded_bits():
+    """FullModelClipAdamW against tests/golden/optim_adamw_bits.json, recorded by tools/record_optim_bits.py on the last commit that
+    stepped AdamW through host-counted kernels of its own: every case of optim_cases on the edge table, three steps, without a
+    scaler and with grad_scale = 1, found_inf = 0 set before every step.  Every hash (p, .grad, exp_avg, exp_avg_sq of every
+    tensor) and bit pattern (last_grad_norm, last_clip_coef) of every step is the recorded one, and the step counts are the steps
+    a tensor had a gradient in.  One test over all twelve runs (about a second): a failure names run, step, tensor and quantity.
+
+    The fixture pins the compiler's sqrtf, division and double pow along with the kernels' own arithmetic.  A toolchain change
+    that moves it is answered by recording again on the last commit that passed, with the new toolchain, never by loosening this
+    test."""
+    with open(RB.DEFAULT_OUT) as f:
+        fixture = json.load(f)
+    chunk = _chunk()
+    assert fixture["header"]["chunk"] == chunk and fixture["header"]["steps"] == RB.STEPS
+    assert set(fixture["cases"]) == set(OC.CASES)
+    fed = RB.inputs(chunk)
+    tensors = OC.edge_tensors(chunk)
+    for case_name, case in RB.cases().items():
+        assert fed["values"] == fixture["inputs"]["values"] and fed["gradients"][case_name] == fixture["inputs"]["gradients"][case_name], (
+            f"{case_name}: the start values or gradients are not the recorded ones (a mismatch on inputs: re-record on the parent)")
+        recorded = fixture["cases"][case_name]
+        taken = [float(sum(t.name not in case.skip.get(step, ()) for step in range(1, RB.STEPS + 1))) for t in tensors]
+        if case_name == "clip_active":
+            assert taken == [2.0 if t.name == "skip" else 3.0 for t in tensors]
+        for run, pre in (("no scaler", None), ("grad_scale 1, found_inf 0", lambda opt: _scalars(opt, 1.0, 0.0))):
+            opt, shots = RB.run_case(case, chunk, DEV, pre_step=pre)
+            torch.cuda.synchronize()
+            assert len(recorded) == len(shots) == RB.STEPS
+            for step, (got, ref) in enumerate(zip(shots, recorded), 1):
+                where = f"{case_name}, {run}, step {step}"
+                for q in ("last_grad_norm", "last_clip_coef"):
+                    assert got[q] == ref[q], f"{where} {q}: {got[q]:#010x}, recorded {ref[q]:#010x} (the arithmetic changed)"
+                for t in tensors:
+                    for q in RB.QUANTITIES:
+                        assert got["tensors"][t.name][q] == ref["tensors"][t.name][q], (
+                            f"{where} {t.name} {q}: not the recorded bits (the arithmetic changed)")
+            sd = opt.state_dict()["state"]
+            assert [float(sd[i]["step"]) for i in range(len(tensors))] == taken, (case_name, run)
 
 
-def test_adamw_switches_to_device_counts_in_mid_run():
-    """Two host-counted steps, then a scaler appears: the counts go up once and step 3 is the step 3 of a run without one."""
+def test_a_scaler_that_appears_in_mid_run_changes_no_bit():
+    """Two steps without a scaler, then one appears: step 3 is the step 3 of a run without one, and the counts are 2 and 3."""
     tensors, case, make, groups, keys, _ = _setup("adamw", "clip_active")
-    _, _, host = _trace(tensors, case, make, groups, keys, (1, 2, 3))
+    _, _, plain = _trace(tensors, case, make, groups, keys, (1, 2, 3))
     _, opt, late = _trace(tensors, case, make, groups, keys, (1, 2, 3),
                           pre_step=lambda i, params, opt: _scalars(opt, 1.0, 0.0) if i == 2 else None)
-    _same(host[2], late[2], "step 3")
+    _same(plain[2], late[2], "step 3")
     sd = opt.state_dict()["state"]
     assert [float(sd[i]["step"]) for i in range(len(tensors))] == [2.0 if t.name == "skip" else 3.0 for t in tensors]
+
+
+@pytest.mark.parametrize("rule", ["adamw", "adam"])
+def test_fresh_state_restarts_the_count(rule):
+    """Two steps, the state of n5 dropped, a third step: n5 gets fresh state and steps as at step 1 from zero moments (the float64
+    formula, held to the contract), the others go on to step 3, and the step that notices waits for nothing."""
+    tensors, case, make, groups, keys, _ = _setup(rule, "clip_active")
+    case = case._replace(skip={})
+    params = OC.make_params(tensors, DEV, torch.float32)
+    opt = make(groups(tensors, params))
+    for step in (1, 2):
+        OC.set_grads(params, OC.gradients(tensors, case, step), DEV)
+        opt.step()
+    given = OC.gradients(tensors, case, 3)
+    OC.set_grads(params, given, DEV)
+    p = params["n5"]
+    del opt.state[p]
+    before = p.detach().double().clone()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        opt.step()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    sd = opt.state_dict()["state"]
+    assert [float(sd[i]["step"]) for i in range(len(tensors))] == [1.0 if t.name == "n5" else 3.0 for t in tensors]
+    i = [t.name for t in tensors].index("n5")
+    total = math.sqrt(sum(float(g.double().pow(2).sum()) for g in given.values()))
+    g = given["n5"].double() * min(1.0, case.max_norm / (total + 1e-6))           # clip_grad_norm_ over the whole table
+    z = torch.zeros_like(g)
+    ref_p, ref_m, ref_v = (OC.adamw64 if rule == "adamw" else RC.adam64)(before.cpu(), g, z, z, 1, **RC.adam_hyper(i))
+    st = opt.state[p]
+    for what, got, ref in (("update", p.detach().double() - before, ref_p - before.cpu()), ("exp_avg", st["exp_avg"].double(), ref_m),
+                           ("exp_avg_sq", st["exp_avg_sq"].double(), ref_v)):
+        err, scale = float((got.cpu() - ref).abs().max()), float(ref.abs().max())
+        print(f"{rule} fresh state, n5 {what}: {err / scale:.2e}")
+        assert err <= OC.RTOL * scale, (rule, what, err, scale)
 
 
 @pytest.mark.parametrize("case_name", ["clip_active", "no_clip", "eps_decides"])

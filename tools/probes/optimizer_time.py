@@ -14,7 +14,7 @@ every step outside the timed region (every step clips when max_norm > 0, as a tr
 --scaler times ``scaler.step(optimizer)`` of a torch.amp.GradScaler instead of ``optimizer.step()`` (the reference's
 AMPTrainer.run_step, :209-246): the gradients are restored multiplied by the scale, and ``scaler.update()`` runs outside the timed
 region.  It adds the variant ``hip_unfused``: the same optimizer with ``_step_supports_amp_scaling = False``, i.e. what a GradScaler
-did with it before it followed the protocol (foreach unscale, ``found_inf.item()``, then the host-counted step).
+did with it before it followed the protocol (foreach unscale, ``found_inf.item()``, then the step without a scale).
 
 Per variant and table two clocks, medians over --reps steps:
     gpu_ms   HIP events recorded around the call on an idle stream: from the first launch's start to the last one's end

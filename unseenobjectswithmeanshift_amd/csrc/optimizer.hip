@@ -1,19 +1,21 @@
-// Full-model-clipped AdamW over a device-resident table of tensors (see include/msm_hip.h: msm_optim_grad_norm,
-// msm_optim_adamw_step, msm_optim_zero).  Reference: Trainer.build_optimizer, MSMFormer/tabletop_train_net_pretrained.py:113-191 --
-// torch.nn.utils.clip_grad_norm_ over every parameter followed by torch.optim.AdamW with one param group per tensor.
+// AdamW, Adam and SGD behind clip_grad_norm_ over a device-resident table of tensors, with GradScaler's fused protocol inside the
+// launches (see include/msm_hip.h: msm_optim_count_norm, msm_optim_update, msm_optim_zero).  Reference: Trainer.build_optimizer,
+// MSMFormer/tabletop_train_net_pretrained.py:113-191 -- torch.nn.utils.clip_grad_norm_ over every parameter followed by
+// torch.optim.AdamW with one param group per tensor -- and torch.optim.Adam / SGD of tools/train_net.py:130-142.
 //
 // The table cuts every tensor into chunks of OPT_CHUNK elements (a 3-element bias is one chunk, a 524 288-element weight 64), and a
 // launch is one workgroup per chunk, whatever the number of tensors:
-//   norm    workgroup c: sum of g^2 over its chunk, in double -> partials[c]; workgroup 0 also advances the call counter
-//   step    workgroup c: adds partials[0 .. n_chunks) (thread t takes t, t + 256, ... in ascending order, then a fixed tree over the
-//           256 threads: every workgroup forms the same bits), total_norm and coef from it, then the AdamW update of its chunk
+//   norm    workgroup c: sum of g^2 over its chunk, in double -> partials[c]; the workgroup of a tensor's first chunk counts its step
+//   update  workgroup c: adds partials[0 .. n_chunks) (thread t takes t, t + 256, ... in ascending order, then a fixed tree over the
+//           256 threads: every workgroup forms the same bits), total_norm and coef from it, then the rule's update of its chunk
 //   zero    workgroup c: g = 0 over its chunk
 // A third launch that sums the partials once would save every workgroup n_chunks L2 reads of 8 bytes (about 17 KiB for the 298
 // tensors of the ResNet-50 head, against the 288 KiB of HBM traffic of a full chunk) and cost a launch and a dependent kernel
 // boundary on a step that is two launches and 0.1 ms long.
-// The counter is written by the norm launch (or the one-thread tick launch that stands in for it when nothing is clipped) and only
-// read by the step launch behind it on the stream.  No atomics, no hand-off between workgroups: bit-identical from call to call
-// for a given table.
+// The step count of a tensor is written by the norm launch (or the one-thread-per-record count launch that stands in for it when
+// nothing is clipped) and only read by the update launch behind it on the stream.  The gradient is unscaled and the step skipped
+// inside the launches (GradScaler's grad_scale / found_inf).  No atomics, no hand-off between workgroups: bit-identical from call
+// to call for a given table.
 #include "common.h"
 
 namespace msm {
@@ -70,117 +72,6 @@ __device__ __forceinline__ double opt_block_sum(double v, double* red) {
     return r;
 }
 
-__global__ __launch_bounds__(OPT_T) void optim_grad_norm_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks,
-                                                                double* __restrict__ partials, int64_t* __restrict__ state, int n_tensors) {
-    __shared__ double red[OPT_T];
-    const int tid = threadIdx.x, c = blockIdx.x;
-    const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, INT32_MAX, MSM_OPTIM_ALIGNED_G);
-    double acc = 0.0;
-    if (k.vec) {
-        const int n4 = k.n & ~3;
-        for (int i = tid * 4; i < n4; i += OPT_T * 4) {
-            const float4 g = *reinterpret_cast<const float4*>(k.g + i);
-            acc = fma((double)g.x, (double)g.x, acc);
-            acc = fma((double)g.y, (double)g.y, acc);
-            acc = fma((double)g.z, (double)g.z, acc);
-            acc = fma((double)g.w, (double)g.w, acc);
-        }
-        if (n4 + tid < k.n) acc = fma((double)k.g[n4 + tid], (double)k.g[n4 + tid], acc);
-    } else {
-        for (int i = tid; i < k.n; i += OPT_T) acc = fma((double)k.g[i], (double)k.g[i], acc);
-    }
-    const double s = opt_block_sum(acc, red);
-    if (tid == 0) {
-        partials[c] = s;
-        if (c == 0) state[0] += 1;
-    }
-}
-
-__global__ void optim_tick_kernel(int64_t* __restrict__ state) { state[0] += 1; }
-
-struct OptScalars {
-    float coef, decay, w1, b2, w2, bc2s, eps, step_size;
-};
-
-__device__ __forceinline__ void opt_update(float& p, float& g, float& m, float& v, const OptScalars& s, bool clip) {
-    if (clip) g *= s.coef;
-    p *= s.decay;
-    m += (g - m) * s.w1;
-    v = v * s.b2 + s.w2 * g * g;
-    p -= s.step_size * (m / (sqrtf(v) / s.bc2s + s.eps));
-}
-
-__global__ __launch_bounds__(OPT_T) void optim_adamw_step_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks,
-                                                                 const double* __restrict__ hyper, const double* __restrict__ partials,
-                                                                 int64_t* __restrict__ state, int n_tensors, int n_chunks, int n_rows,
-                                                                 float max_norm) {
-    __shared__ double red[OPT_T];
-    __shared__ OptScalars sh;
-    const int tid = threadIdx.x, c = blockIdx.x;
-    const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, n_rows, MSM_OPTIM_ALIGNED);
-    double total = 0.0, coef = 1.0;
-    if (max_norm > 0.f) {
-        double a = 0.0;
-        for (int j = tid; j < n_chunks; j += OPT_T) a += partials[j];
-        total = sqrt(opt_block_sum(a, red));
-        const double q = (double)max_norm / (total + 1e-6);
-        coef = q > 1.0 ? 1.0 : q;               // a nan norm stays a nan coefficient, as torch's clamp(max=1) leaves it
-    }
-    if (tid == 0) {
-        const double* h = hyper + (int64_t)k.row * OPT_HYP;
-        const double lr = h[0], wd = h[1], b1 = h[2], b2 = h[3], eps = h[4];
-        const double step = (double)(state[0] - (int64_t)h[5]);
-        const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
-        OptScalars s;
-        s.coef = (float)coef;
-        s.decay = (float)(1.0 - lr * wd);
-        s.w1 = (float)(1.0 - b1);
-        s.b2 = (float)b2;
-        s.w2 = (float)(1.0 - b2);
-        s.bc2s = (float)sqrt(bc2);
-        s.eps = (float)eps;
-        s.step_size = (float)(lr / bc1);
-        sh = s;
-        if (c == 0) {
-            float* out = reinterpret_cast<float*>(state + 1);
-            out[0] = (float)total;
-            out[1] = s.coef;
-        }
-    }
-    __syncthreads();
-    const OptScalars s = sh;
-    const bool clip = s.coef != 1.f;            // coef == 1 leaves every g as it is: no store
-    if (k.vec) {
-        const int n4 = k.n & ~3;
-        for (int i = tid * 4; i < n4; i += OPT_T * 4) {
-            float4 p = *reinterpret_cast<const float4*>(k.p + i), g = *reinterpret_cast<const float4*>(k.g + i);
-            float4 m = *reinterpret_cast<const float4*>(k.m + i), v = *reinterpret_cast<const float4*>(k.v + i);
-            opt_update(p.x, g.x, m.x, v.x, s, clip);
-            opt_update(p.y, g.y, m.y, v.y, s, clip);
-            opt_update(p.z, g.z, m.z, v.z, s, clip);
-            opt_update(p.w, g.w, m.w, v.w, s, clip);
-            *reinterpret_cast<float4*>(k.p + i) = p;
-            *reinterpret_cast<float4*>(k.m + i) = m;
-            *reinterpret_cast<float4*>(k.v + i) = v;
-            if (clip) *reinterpret_cast<float4*>(k.g + i) = g;
-        }
-        const int i = n4 + tid;
-        if (i < k.n) {
-            float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
-            opt_update(p, g, m, v, s, clip);
-            k.p[i] = p, k.m[i] = m, k.v[i] = v;
-            if (clip) k.g[i] = g;
-        }
-    } else {
-        for (int i = tid; i < k.n; i += OPT_T) {
-            float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
-            opt_update(p, g, m, v, s, clip);
-            k.p[i] = p, k.m[i] = m, k.v[i] = v;
-            if (clip) k.g[i] = g;
-        }
-    }
-}
-
 __global__ __launch_bounds__(OPT_T) void optim_zero_kernel(const int64_t* __restrict__ tensors, const int64_t* __restrict__ chunks, int n_tensors) {
     const int tid = threadIdx.x, c = blockIdx.x;
     const OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, INT32_MAX, MSM_OPTIM_ALIGNED_G);
@@ -192,10 +83,6 @@ __global__ __launch_bounds__(OPT_T) void optim_zero_kernel(const int64_t* __rest
         for (int i = tid; i < k.n; i += OPT_T) k.g[i] = 0.f;
     }
 }
-
-// ---- the rule entries (msm_optim_count_norm, msm_optim_update): AdamW, Adam and SGD with step counts on the device, the gradient
-// unscaled and the step skipped inside the launches (GradScaler's grad_scale / found_inf).  Same table, same chunk per workgroup, same
-// order of the partials; the count of a tensor is written by the launch in front of the one that reads it.
 
 // *found_inf != 0 (a nan too): the step is not taken.  The same word for every workgroup of both launches of a step.
 __device__ __forceinline__ bool opt_skipped(const float* __restrict__ found_inf) { return found_inf != nullptr && !(*found_inf == 0.f); }
@@ -256,44 +143,43 @@ __global__ __launch_bounds__(OPT_T) void optim_count_kernel(const int64_t* __res
     steps[row] += 1;
 }
 
-struct OptRuleScalars {
-    OptScalars a;                               // AdamW's, as the kernel above prepares them (Adam: without decay)
-    float inv_scale, wd, lr, momentum, undamped;
+struct OptScalars {                          // of one hyper row and step, prepared once per workgroup in double
+    float coef, inv_scale;
+    float decay, w1, b2, w2, bc2s, eps, step_size;          // AdamW and Adam (Adam: without decay)
+    float wd, lr, momentum, undamped;                       // Adam and SGD add wd p to the gradient; the rest is SGD's
     int first, nesterov;
 };
 
-// AdamW on one element as optim_adamw_step_kernel computes it.  The compiler fuses different products of opt_update into an fma in
-// each of that kernel's three loops (none in the scalar loop; m, v and p in the 16-byte loop; m alone in the numel % 4 tail), and
-// chooses again in any other kernel the function is inlined into, so the same source does not give the same bits.  The three
-// forms are spelled out here, with contraction off, for the AdamW rule to agree with that kernel bit for bit
-// (tests/test_gpu_optim_scaler.py holds the two to equal bits on every path).
+// The access path of an element: the scalar loop (a tensor that is not 16-byte aligned), the 16-byte loop, the numel % 4 tail behind it
 constexpr int OPT_FORM_SCALAR = 0, OPT_FORM_VEC = 1, OPT_FORM_TAIL = 2;
 
-template <int FORM>
-__device__ __forceinline__ void opt_update_as(float& p, float& g, float& m, float& v, const OptScalars& s, float inv, bool unscale, bool clip) {
-#pragma clang fp contract(off)
-    if (unscale) g = g * inv;
-    if (clip) g = g * s.coef;
-    const float d = g - m, gg = s.w2 * g, vb = v * s.b2;
-    m = FORM == OPT_FORM_SCALAR ? m + d * s.w1 : __builtin_fmaf(s.w1, d, m);
-    v = FORM == OPT_FORM_VEC ? __builtin_fmaf(g, gg, vb) : vb + gg * g;
-    const float q = s.step_size * (m / (sqrtf(v) / s.bc2s + s.eps));
-    p = FORM == OPT_FORM_VEC ? __builtin_fmaf(s.decay, p, -q) : p * s.decay - q;
-}
-
-// Adam and SGD on one element, every operation rounded on its own (no fma: the compiler's choice of which products to fuse may not
-// differ between the loops, or between a scaled and an unscaled step)
-template <int RULE>
-__device__ __forceinline__ void opt_rule_update(float& p, float& g, float& m, float& v, const OptRuleScalars& s, bool unscale, bool clip) {
+// One element of a rule.  Contraction is off: every operation below is rounded on its own unless it is written as an fma.
+// AdamW's arithmetic is defined per access path, and the three forms are this project's AdamW (include/msm_hip.h states them;
+// tests/golden/optim_adamw_bits.json pins their bits):
+//   OPT_FORM_SCALAR  no fma
+//   OPT_FORM_VEC     m, v and p fused
+//   OPT_FORM_TAIL    m alone fused
+// Adam and SGD have one form, without an fma: the compiler's choice of which products to fuse may not differ between the loops, or
+// between a scaled and an unscaled step.
+template <int RULE, int FORM>
+__device__ __forceinline__ void opt_rule_update(float& p, float& g, float& m, float& v, const OptScalars& s, bool unscale, bool clip) {
 #pragma clang fp contract(off)
     if (unscale) g = g * s.inv_scale;
-    if (clip) g *= s.a.coef;
+    if (clip) g = g * s.coef;
+    if (RULE == MSM_OPTIM_ADAMW) {
+        const float d = g - m, gg = s.w2 * g, vb = v * s.b2;
+        m = FORM == OPT_FORM_SCALAR ? m + d * s.w1 : __builtin_fmaf(s.w1, d, m);
+        v = FORM == OPT_FORM_VEC ? __builtin_fmaf(g, gg, vb) : vb + gg * g;
+        const float q = s.step_size * (m / (sqrtf(v) / s.bc2s + s.eps));
+        p = FORM == OPT_FORM_VEC ? __builtin_fmaf(s.decay, p, -q) : p * s.decay - q;
+        return;
+    }
     float d = g;                                // g + wd p is not written back
     if (s.wd != 0.f) d = g + s.wd * p;
     if (RULE == MSM_OPTIM_ADAM) {
-        m += (d - m) * s.a.w1;
-        v = v * s.a.b2 + s.a.w2 * d * d;
-        p -= s.a.step_size * (m / (sqrtf(v) / s.a.bc2s + s.a.eps));
+        m += (d - m) * s.w1;
+        v = v * s.b2 + s.w2 * d * d;
+        p -= s.step_size * (m / (sqrtf(v) / s.bc2s + s.eps));
     } else {
         if (s.momentum != 0.f) {
             m = s.first ? d : s.momentum * m + s.undamped * d;
@@ -310,7 +196,7 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
                                                              const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
                                                              int n_tensors, int n_chunks, int n_rows, float max_norm) {
     __shared__ double red[OPT_T];
-    __shared__ OptRuleScalars sh;
+    __shared__ OptScalars sh;
     if (opt_skipped(found_inf)) return;         // the whole grid alike: p, the state, .grad and the state block stay as they are
     const int tid = threadIdx.x, c = blockIdx.x;
     OptChunk k = opt_chunk(tensors, chunks, c, n_tensors, n_rows, MSM_OPTIM_ALIGNED);
@@ -327,28 +213,28 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
         for (int j = tid; j < n_chunks; j += OPT_T) a += partials[j];
         total = sqrt(opt_block_sum(a, red));
         const double q = (double)max_norm / (total + 1e-6);
-        coef = q > 1.0 ? 1.0 : q;
+        coef = q > 1.0 ? 1.0 : q;               // a nan norm stays a nan coefficient, as torch's clamp(max=1) leaves it
     }
     if (tid == 0) {
         const double lr = h[0], wd = h[1], b1 = h[2], b2 = h[3], eps = h[4];
         const int64_t count = steps[k.row];
-        OptRuleScalars s;
-        s.a.coef = (float)coef;
-        s.a.decay = (float)(1.0 - lr * wd);
-        s.a.w1 = (float)(1.0 - b1);
-        s.a.b2 = (float)b2;
-        s.a.w2 = (float)(1.0 - b2);
-        s.a.eps = (float)eps;
+        OptScalars s;
+        s.coef = (float)coef;
+        s.inv_scale = opt_inv_scale(grad_scale);
+        s.decay = (float)(1.0 - lr * wd);
+        s.w1 = (float)(1.0 - b1);
+        s.b2 = (float)b2;
+        s.w2 = (float)(1.0 - b2);
+        s.eps = (float)eps;
         if (RULE == MSM_OPTIM_SGD) {
-            s.a.bc2s = 1.f;
-            s.a.step_size = (float)lr;
+            s.bc2s = 1.f;
+            s.step_size = (float)lr;
         } else {
             const double step = (double)count;
             const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
-            s.a.bc2s = (float)sqrt(bc2);
-            s.a.step_size = (float)(lr / bc1);
+            s.bc2s = (float)sqrt(bc2);
+            s.step_size = (float)(lr / bc1);
         }
-        s.inv_scale = opt_inv_scale(grad_scale);
         s.wd = (float)wd;
         s.lr = (float)lr;
         s.momentum = (float)h[5];
@@ -359,50 +245,16 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
         if (c == 0) {
             float* out = reinterpret_cast<float*>(state + 1);
             out[0] = (float)total;
-            out[1] = s.a.coef;
+            out[1] = s.coef;
         }
     }
     __syncthreads();
-    const OptRuleScalars s = sh;
-    const bool clip = s.a.coef != 1.f;
-    // g is unscaled in registers right after its load (inv = 1 without a scale: no multiply) and written back whenever it changed;
-    // every product of the element functions is rounded on its own, so a step with a power-of-two scale forms the bits of one without
+    const OptScalars s = sh;
+    const bool clip = s.coef != 1.f;            // coef == 1 leaves every g as it is
+    // g is unscaled in registers right after its load (no multiply without a scale) and written back whenever it changed; the
+    // unscaling product is rounded on its own, so a step with a power-of-two scale forms the bits of one without
     const bool unscale = grad_scale != nullptr;
     const bool store_g = unscale || clip;
-    const float inv = s.inv_scale;
-    if (RULE == MSM_OPTIM_ADAMW) {              // the three loops of optim_adamw_step_kernel, each in its form
-        const OptScalars a = s.a;
-        if (k.vec) {
-            const int n4 = k.n & ~3;
-            for (int i = tid * 4; i < n4; i += OPT_T * 4) {
-                float4 p = *reinterpret_cast<const float4*>(k.p + i), g = *reinterpret_cast<const float4*>(k.g + i);
-                float4 m = *reinterpret_cast<const float4*>(k.m + i), v = *reinterpret_cast<const float4*>(k.v + i);
-                opt_update_as<OPT_FORM_VEC>(p.x, g.x, m.x, v.x, a, inv, unscale, clip);
-                opt_update_as<OPT_FORM_VEC>(p.y, g.y, m.y, v.y, a, inv, unscale, clip);
-                opt_update_as<OPT_FORM_VEC>(p.z, g.z, m.z, v.z, a, inv, unscale, clip);
-                opt_update_as<OPT_FORM_VEC>(p.w, g.w, m.w, v.w, a, inv, unscale, clip);
-                *reinterpret_cast<float4*>(k.p + i) = p;
-                *reinterpret_cast<float4*>(k.m + i) = m;
-                *reinterpret_cast<float4*>(k.v + i) = v;
-                if (store_g) *reinterpret_cast<float4*>(k.g + i) = g;
-            }
-            const int i = n4 + tid;
-            if (i < k.n) {
-                float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
-                opt_update_as<OPT_FORM_TAIL>(p, g, m, v, a, inv, unscale, clip);
-                k.p[i] = p, k.m[i] = m, k.v[i] = v;
-                if (store_g) k.g[i] = g;
-            }
-        } else {
-            for (int i = tid; i < k.n; i += OPT_T) {
-                float p = k.p[i], g = k.g[i], m = k.m[i], v = k.v[i];
-                opt_update_as<OPT_FORM_SCALAR>(p, g, m, v, a, inv, unscale, clip);
-                k.p[i] = p, k.m[i] = m, k.v[i] = v;
-                if (store_g) k.g[i] = g;
-            }
-        }
-        return;
-    }
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (k.vec) {
         const int n4 = k.n & ~3;
@@ -410,10 +262,10 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
             float4 p = *reinterpret_cast<const float4*>(k.p + i), g = *reinterpret_cast<const float4*>(k.g + i);
             float4 m = use_m ? *reinterpret_cast<const float4*>(k.m + i) : z4;
             float4 v = USE_V ? *reinterpret_cast<const float4*>(k.v + i) : z4;
-            opt_rule_update<RULE>(p.x, g.x, m.x, v.x, s, unscale, clip);
-            opt_rule_update<RULE>(p.y, g.y, m.y, v.y, s, unscale, clip);
-            opt_rule_update<RULE>(p.z, g.z, m.z, v.z, s, unscale, clip);
-            opt_rule_update<RULE>(p.w, g.w, m.w, v.w, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_VEC>(p.x, g.x, m.x, v.x, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_VEC>(p.y, g.y, m.y, v.y, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_VEC>(p.z, g.z, m.z, v.z, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_VEC>(p.w, g.w, m.w, v.w, s, unscale, clip);
             *reinterpret_cast<float4*>(k.p + i) = p;
             if (use_m) *reinterpret_cast<float4*>(k.m + i) = m;
             if (USE_V) *reinterpret_cast<float4*>(k.v + i) = v;
@@ -422,7 +274,7 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
         const int i = n4 + tid;
         if (i < k.n) {
             float p = k.p[i], g = k.g[i], m = use_m ? k.m[i] : 0.f, v = USE_V ? k.v[i] : 0.f;
-            opt_rule_update<RULE>(p, g, m, v, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_TAIL>(p, g, m, v, s, unscale, clip);
             k.p[i] = p;
             if (use_m) k.m[i] = m;
             if (USE_V) k.v[i] = v;
@@ -431,7 +283,7 @@ __global__ __launch_bounds__(OPT_T) void optim_update_kernel(const int64_t* __re
     } else {
         for (int i = tid; i < k.n; i += OPT_T) {
             float p = k.p[i], g = k.g[i], m = use_m ? k.m[i] : 0.f, v = USE_V ? k.v[i] : 0.f;
-            opt_rule_update<RULE>(p, g, m, v, s, unscale, clip);
+            opt_rule_update<RULE, OPT_FORM_SCALAR>(p, g, m, v, s, unscale, clip);
             k.p[i] = p;
             if (use_m) k.m[i] = m;
             if (USE_V) k.v[i] = v;
@@ -448,38 +300,6 @@ static bool opt_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 using namespace msm;
 
 extern "C" int msm_optim_chunk(void) { return OPT_CHUNK; }
-
-extern "C" int msm_optim_grad_norm(const int64_t* tensors, const int64_t* chunks, double* partials, int64_t* state, int n_tensors,
-                                   int n_chunks, void* stream) {
-    MSM_REQUIRE(tensors && chunks && partials && state, "msm_optim_grad_norm: null pointer");
-    MSM_REQUIRE(opt_aligned8(tensors) && opt_aligned8(chunks) && opt_aligned8(partials) && opt_aligned8(state),
-                "msm_optim_grad_norm: the tables, the partials and the state block must be 8-byte aligned");
-    MSM_REQUIRE(n_tensors >= 1 && n_chunks >= n_tensors, "msm_optim_grad_norm: n_tensors = %d, n_chunks = %d (every tensor has a chunk)",
-                n_tensors, n_chunks);
-    optim_grad_norm_kernel<<<n_chunks, OPT_T, 0, (hipStream_t)stream>>>(tensors, chunks, partials, state, n_tensors);
-    MSM_CHECK_LAUNCH("msm_optim_grad_norm");
-    return MSM_OK;
-}
-
-extern "C" int msm_optim_adamw_step(const int64_t* tensors, const int64_t* chunks, const double* hyper, const double* partials,
-                                    int64_t* state, int n_tensors, int n_chunks, int n_rows, float max_norm, void* stream) {
-    MSM_REQUIRE(tensors && chunks && hyper && state, "msm_optim_adamw_step: null pointer");
-    MSM_REQUIRE(!(max_norm > 0.f) || partials, "msm_optim_adamw_step: max_norm > 0 needs the partials of msm_optim_grad_norm");
-    MSM_REQUIRE(opt_aligned8(tensors) && opt_aligned8(chunks) && opt_aligned8(hyper) && opt_aligned8(partials) && opt_aligned8(state),
-                "msm_optim_adamw_step: the tables, the partials and the state block must be 8-byte aligned");
-    MSM_REQUIRE(n_tensors >= 1 && n_chunks >= n_tensors && n_rows >= 1,
-                "msm_optim_adamw_step: n_tensors = %d, n_chunks = %d, n_rows = %d (every tensor has a chunk and a row)", n_tensors, n_chunks,
-                n_rows);
-    MSM_REQUIRE(max_norm == max_norm, "msm_optim_adamw_step: max_norm is nan");
-    if (!(max_norm > 0.f)) {
-        optim_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(state);
-        MSM_CHECK_LAUNCH("msm_optim_adamw_step(counter)");
-    }
-    optim_adamw_step_kernel<<<n_chunks, OPT_T, 0, (hipStream_t)stream>>>(tensors, chunks, hyper, partials, state, n_tensors, n_chunks,
-                                                                        n_rows, max_norm);
-    MSM_CHECK_LAUNCH("msm_optim_adamw_step");
-    return MSM_OK;
-}
 
 extern "C" int msm_optim_count_norm(const int64_t* tensors, const int64_t* chunks, double* partials, int64_t* steps, const float* grad_scale,
                                     const float* found_inf, int n_tensors, int n_chunks, int n_rows, void* stream) {

@@ -1907,9 +1907,9 @@ def embloss_info(info, B):
     return dict(K=info[0], status=info[1], flag=info[2], n=info[4:4 + B * Kt].view(B, Kt), N=info[4 + B * Kt:].view(B, Kt))
 
 
-# ---- optimizer (optim.py): full-model-clipped AdamW over a device-resident table of tensors ----
-OPTIM_REC = 8           # int64 per tensor record: p, g, exp_avg, exp_avg_sq addresses, numel, hyper row, flags, 0
-OPTIM_HYP = 8           # doubles per hyper-parameter row: lr, weight_decay, beta1, beta2, eps, step offset, 0, 0
+# ---- optimizers (optim.py): clip_grad_norm_ + AdamW, Adam or SGD over a device-resident table of tensors, step counts on the device ----
+OPTIM_REC = 8           # int64 per tensor record: p, g, exp_avg, exp_avg_sq addresses, numel, row (of hyper and steps), flags, 0
+OPTIM_HYP = 8           # doubles per hyper-parameter row: lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov
 OPTIM_ALIGNED = 1       # MSM_OPTIM_ALIGNED: p, g, exp_avg and exp_avg_sq are all 16-byte aligned
 OPTIM_ALIGNED_G = 2     # MSM_OPTIM_ALIGNED_G: g is
 
@@ -1926,32 +1926,7 @@ def _optim_tables(tensors, chunks, n_tensors, n_chunks):
                            f"{n_chunks} chunks need {2 * n_chunks} (got {chunks.numel()}), every tensor has a chunk")
 
 
-def optim_grad_norm(tensors, chunks, partials, state, n_tensors, n_chunks):
-    """msm_optim_grad_norm: partials[c] = sum of g^2 over chunk c (double) and state[0] += 1, one launch.  tensors / chunks: int64
-    device tables in the layout of include/msm_hip.h, partials float64 (n_chunks,), state int64 (2,)."""
-    _optim_tables(tensors, chunks, n_tensors, n_chunks)
-    _c(partials, "partials", torch.float64), _c(state, "state", torch.int64)
-    if partials.numel() < n_chunks or state.numel() < 2:
-        raise RuntimeError(f"optim_grad_norm: partials needs {n_chunks} doubles (got {partials.numel()}), state 2 int64")
-    check(lib().msm_optim_grad_norm(_p(tensors), _p(chunks), _p(partials), _p(state), n_tensors, n_chunks, _stream()),
-          "msm_optim_grad_norm")
-
-
-def optim_adamw_step(tensors, chunks, hyper, partials, state, n_tensors, n_chunks, n_rows, max_norm):
-    """msm_optim_adamw_step: clip coefficient from the partials of optim_grad_norm (max_norm > 0; else no clipping, partials may be
-    None and the call advances the counter itself) and torch's AdamW on every chunk, one launch.  hyper float64 (n_rows, 8)."""
-    _optim_tables(tensors, chunks, n_tensors, n_chunks)
-    _c(hyper, "hyper", torch.float64), _c(partials, "partials", torch.float64), _c(state, "state", torch.int64)
-    if n_rows < 1 or hyper.numel() < n_rows * OPTIM_HYP or state.numel() < 2 or (
-            max_norm > 0 and (partials is None or partials.numel() < n_chunks)):
-        raise RuntimeError(f"optim_adamw_step: {n_rows} rows need {n_rows * OPTIM_HYP} doubles (got {hyper.numel()}), state 2 int64, "
-                           f"max_norm > 0 partials of {n_chunks} doubles")
-    check(lib().msm_optim_adamw_step(_p(tensors), _p(chunks), _p(hyper), _p(partials), _p(state), n_tensors, n_chunks, n_rows,
-                                     float(max_norm), _stream()), "msm_optim_adamw_step")
-
-
 OPTIM_RULES = {"adamw": 0, "adam": 1, "sgd": 2}        # MSM_OPTIM_ADAMW, MSM_OPTIM_ADAM, MSM_OPTIM_SGD
-# hyper-parameter row of the rule entries: lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov
 
 
 def _optim_scalar(t, name, device):
@@ -1967,7 +1942,8 @@ def _optim_scalar(t, name, device):
 
 def optim_count_norm(tensors, chunks, partials, steps, n_tensors, n_chunks, n_rows, grad_scale=None, found_inf=None):
     """msm_optim_count_norm: partials[c] = sum of (g / grad_scale)^2 over chunk c (double) and steps[row] += 1 for every tensor of
-    the table unless found_inf says the step is skipped, one launch.  steps int64 (n_rows,)."""
+    the table unless found_inf says the step is skipped, one launch.  tensors / chunks: int64 device tables in the layout of
+    include/msm_hip.h, partials float64 (n_chunks,), steps int64 (n_rows,)."""
     _optim_tables(tensors, chunks, n_tensors, n_chunks)
     _c(partials, "partials", torch.float64), _c(steps, "steps", torch.int64)
     if partials.numel() < n_chunks or n_rows < 1 or steps.numel() < n_rows:

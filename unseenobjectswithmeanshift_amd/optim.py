@@ -11,8 +11,8 @@ update per chunk (the definition is in include/msm_hip.h).  Nothing in ``step()`
     sum(losses.values()).backward(); optimizer.step(); optimizer.zero_grad()
 
 ``SGD`` and ``Adam`` are the optimizers of the UCN embedding network (tools/train_net.py:130-142: two param groups, biases then
-weights; ``build_ucn_optimizer``) on the same table, chunk list and uploads, through the rule entries of the library
-(msm_optim_count_norm / msm_optim_update), which keep the step count of every tensor on the device.  All three classes follow
+weights; ``build_ucn_optimizer``) on the same table, chunk list, uploads and launches (msm_optim_count_norm / msm_optim_update,
+one rule per optimizer), which keep the step count of every tensor on the device.  All three classes follow
 GradScaler's protocol for fused optimizers (``_step_supports_amp_scaling``: the scaler sets ``grad_scale`` and ``found_inf``, the
 kernels unscale and skip), so the reference's ``grad_scaler.step(optimizer)`` (AMPTrainer.run_step, :209-246) does not wait either:
 
@@ -79,22 +79,19 @@ class _TableOptimizer(torch.optim.Optimizer):
     launches of a step, ``zero_grad`` in one launch, the state dicts.  A subclass names its rule, the hyper-parameters of a group
     (``_hyper_of``, ``_group_rows``) and its per-parameter state (``_state_of``, ``_write_counts``, ``_loaded_counts``).
 
-    Step counts: with ``_device_counts`` they live in ``_steps_dev`` (int64 per parameter), advanced by the launches for the tensors
-    that take a step, and the step goes through the rule entries, which also take GradScaler's ``grad_scale`` / ``found_inf``.
-    Without (``FullModelClipAdamW`` until it first meets a scaler) the host derives them from the call counter, as it always did."""
+    Step counts live in ``_steps_dev`` (int64 per parameter), advanced by the launches for the tensors that take a step -- a step
+    that GradScaler's ``found_inf`` skips is decided there, where no host counter could follow."""
 
     _NAME = None
     _RULE = None
     _hyper_of = None
     _step_supports_amp_scaling = True       # torch/amp/grad_scaler.py:403-454: the scaler sets grad_scale / found_inf and calls step()
 
-    def _setup(self, max_norm, device_counts):
+    def _setup(self, max_norm):
         self.max_norm = float(max_norm)
         self.uploads = 0
         self.last_grad_norm = None
         self.last_clip_coef = None
-        self._device_counts = device_counts
-        self._calls = 0                 # value of the device call counter once everything issued has run (host-counted steps)
         self._params = None             # flat parameter list; everything below is built from it at the first step
         self._seen = set()              # indices of the parameters that an earlier table held (their device counts may have moved)
 
@@ -108,10 +105,9 @@ class _TableOptimizer(torch.optim.Optimizer):
             if not p.is_contiguous():
                 raise RuntimeError(f"{self._NAME}: parameter of shape {tuple(p.shape)} is not contiguous")
         if getattr(self, "_params", None) is not None:
-            self._layout(keep_offsets=True)
+            self._layout(keep_counts=True)
 
-    def _layout(self, keep_offsets=False):
-        old = dict(zip(map(id, self._params), self._off)) if keep_offsets else {}
+    def _layout(self, keep_counts=False):
         params = [p for g in self.param_groups for p in g["params"]]
         for p in params:
             if not p.is_cuda:
@@ -122,7 +118,6 @@ class _TableOptimizer(torch.optim.Optimizer):
             if p.numel() == 0:
                 raise RuntimeError(f"{self._NAME}: a parameter without elements")
         self._params = params
-        self._off = [old.get(id(p), self._calls) for p in params]           # step of parameter i = calls - off[i] (host-counted)
         self._group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
         chunk = self.chunk = ops.optim_chunk()
         self._chunk_offsets = [np.arange(0, p.numel(), chunk, dtype=np.int64) for p in params]
@@ -138,20 +133,15 @@ class _TableOptimizer(torch.optim.Optimizer):
         self._partials = torch.zeros(C, dtype=torch.float64, device=dev)
         if getattr(self, "_state_dev", None) is None or self._state_dev.device != dev:
             self._state_dev = torch.zeros(2, dtype=torch.int64, device=dev)
-            if self._calls:
-                self._state_dev[:1].fill_(self._calls)       # a launch: the first step may run where nothing may wait
             f = self._state_dev.view(torch.float32)
             self.last_grad_norm, self.last_clip_coef = f[2], f[3]
-        if self._device_counts:             # a parameter group added later: the counts of the parameters before it stay
-            steps = torch.zeros(T, dtype=torch.int64, device=dev)
-            before = getattr(self, "_steps_dev", None) if keep_offsets else None
-            if before is not None:
-                steps[:before.numel()].copy_(before)
-            self._steps_dev = steps
+        steps = torch.zeros(T, dtype=torch.int64, device=dev)
+        if keep_counts:                    # a parameter group added later: the counts of the parameters before it stay
+            steps[:self._steps_dev.numel()].copy_(self._steps_dev)
+        self._steps_dev = steps
         self._slots = [_Slot(self._words), _Slot(self._words)]
         self._hyper_key = self._table_key = None
-        self._present, self._absent = [], []
-        self._n_tensors = self._n_chunks = 0
+        self._n_tensors = self._n_chunks = self._n_states = 0
 
     # ---- host mirror and upload ----
     def _free_slot(self):
@@ -169,16 +159,9 @@ class _TableOptimizer(torch.optim.Optimizer):
         slot.event.record()
         self.uploads += 1
 
-    def _upload_counts(self, counts):
-        """The step counts of every parameter, known to the host at this moment, to the device: one asynchronous copy."""
-        staged = torch.tensor(counts, dtype=torch.int64).pin_memory()
-        self._steps_dev = staged.to(self._device, non_blocking=True)
-
     def _hyper_rows(self, key):
         rows = np.zeros((len(self._params), ops.OPTIM_HYP), dtype=np.float64)
         rows[:] = self._group_rows(key)[self._group_of]
-        if not self._device_counts:
-            rows[:, 5] = self._off
         return rows.ravel()
 
     def _table_extra(self):
@@ -226,16 +209,15 @@ class _TableOptimizer(torch.optim.Optimizer):
         hyper_key = list(map(self._hyper_of, self.param_groups))        # ~0.1 ms of Python per step for 298 groups: no
         gptrs = [0 if g is None else g.data_ptr() for g in [p.grad for p in params]]      # per-group work beyond these lines
         table_key = (gptrs, list(map(_DATA_PTR, params)), self._table_extra())
-        if table_key != self._table_key:
+        # a state that the user dropped (del optimizer.state[p]) took its tensors with it: new state, new records
+        if table_key != self._table_key or len(self.state) != self._n_states:
             present, rec, chunks = self._records(gptrs)
-            seen = set(present)
             slot = self._free_slot()
             slot.f64[:self._rec0] = self._hyper_rows(hyper_key)
             slot.i64[self._rec0:self._rec0 + rec.size] = rec.ravel()
             slot.i64[self._chk0:self._chk0 + chunks.size] = chunks.ravel()
-            self._present, self._absent = present, [i for i in range(len(params)) if i not in seen]
-            self._seen |= seen
-            self._n_tensors, self._n_chunks = len(present), len(chunks)
+            self._seen.update(present)
+            self._n_tensors, self._n_chunks, self._n_states = len(present), len(chunks), len(self.state)
             if present:
                 self._upload(slot, self._chk0 + chunks.size)
             self._table_key, self._hyper_key = table_key, hyper_key
@@ -255,31 +237,14 @@ class _TableOptimizer(torch.optim.Optimizer):
         # Only their addresses are used: the kernels read the values.
         grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         with torch.cuda.device(self._device if self._params is not None else self._first_device()):
-            if not self._device_counts and (grad_scale is not None or found_inf is not None):
-                # a skipped step is decided on the device, where the host's call counter cannot follow: from here on the counts
-                # live there.  The host knows them exactly at this moment.
-                if self._params is None:
-                    self._layout()
-                self._upload_counts([self._calls - o for o in self._off])
-                self._device_counts = True
-                self._hyper_key = None
             self._prepare()
             if not self._n_tensors:
                 return None
             n, c, rows = self._n_tensors, self._n_chunks, len(self._params)
-            if self._device_counts:
-                if self.max_norm > 0:
-                    ops.optim_count_norm(self._rec_dev, self._chk_dev, self._partials, self._steps_dev, n, c, rows, grad_scale, found_inf)
-                ops.optim_update(self._RULE, self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev,
-                                 self._steps_dev, n, c, rows, self.max_norm, grad_scale, found_inf)
-                return None
             if self.max_norm > 0:
-                ops.optim_grad_norm(self._rec_dev, self._chk_dev, self._partials, self._state_dev, n, c)
-            ops.optim_adamw_step(self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev, n, c, rows,
-                                 self.max_norm)
-        self._calls += 1
-        for i in self._absent:              # the counter moved, their step did not
-            self._off[i] += 1
+                ops.optim_count_norm(self._rec_dev, self._chk_dev, self._partials, self._steps_dev, n, c, rows, grad_scale, found_inf)
+            ops.optim_update(self._RULE, self._rec_dev, self._chk_dev, self._hyper_dev, self._partials, self._state_dev,
+                             self._steps_dev, n, c, rows, self.max_norm, grad_scale, found_inf)
         return None
 
     def _first_device(self):
@@ -301,25 +266,18 @@ class _TableOptimizer(torch.optim.Optimizer):
             if self._n_tensors:
                 ops.optim_zero(self._rec_dev, self._chk_dev, self._n_tensors, self._n_chunks)
 
-    def _counts(self):
-        """Steps taken per parameter; device counts are read back here (a wait: state_dict() may, step() may not)."""
-        if self._device_counts:
-            return self._steps_dev.cpu().tolist()
-        return [self._calls - o for o in self._off]
-
     def state_dict(self):
-        """torch's layout; the step counts are materialised here (``step`` a float32 scalar, as torch keeps it).  With the counts on
-        the device a parameter that has not stepped -- every step since its state was made was skipped -- is written out as torch
-        would have it: without state."""
+        """torch's layout; the step counts are read back from the device and materialised here (``step`` a float32 scalar, as torch
+        keeps it): a wait, which state_dict() may and step() may not.  A parameter that has not stepped -- every step since its
+        state was made was skipped -- is written out as torch would have it: without state."""
         if self._params is None:
             return super().state_dict()
-        counts = self._counts()
+        counts = self._steps_dev.cpu().tolist()
         self._write_counts(counts)
         sd = super().state_dict()
-        if self._device_counts:
-            for i, n in enumerate(counts):
-                if n == 0:
-                    sd["state"].pop(i, None)
+        for i, n in enumerate(counts):
+            if n == 0:
+                sd["state"].pop(i, None)
         return sd
 
     def load_state_dict(self, state_dict):
@@ -327,12 +285,10 @@ class _TableOptimizer(torch.optim.Optimizer):
         if self._params is None:
             with torch.cuda.device(self._first_device()):
                 self._layout()
-        counts = self._loaded_counts()
-        if self._device_counts:
-            self._upload_counts(counts)
-        else:
-            self._off = [self._calls - n for n in counts]
-        self._hyper_key = self._table_key = None         # new state tensors, new offsets: the next step uploads the table
+        # the loaded step counts to the device: one asynchronous copy
+        staged = torch.tensor(self._loaded_counts(), dtype=torch.int64).pin_memory()
+        self._steps_dev = staged.to(self._device, non_blocking=True)
+        self._hyper_key = self._table_key = None         # new state tensors: the next step uploads the table
 
 
 class _AdamFamily(_TableOptimizer):
@@ -369,7 +325,8 @@ class _AdamFamily(_TableOptimizer):
             st["step"] = torch.tensor(0.0)
             st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            self._off[i] = self._calls
+            if i in self._seen:         # its state was dropped after it had stepped: it starts again at step 1, as in torch
+                self._steps_dev[i:i + 1].fill_(0)
         m, v = st["exp_avg"], st["exp_avg_sq"]
         self._check_state(i, p, (("exp_avg", m), ("exp_avg_sq", v)))
         return m, v
@@ -404,8 +361,11 @@ class FullModelClipAdamW(_AdamFamily):
     Under a ``torch.amp.GradScaler`` (``scaler.step(optimizer)``) the kernels unscale the gradients and skip the step when the
     scaler found an inf: no parameter, state or step count changes, ``last_grad_norm`` / ``last_clip_coef`` keep the last taken
     step's values, and ``.grad`` stays scaled (the reference's ``unscale_`` has divided it by then; nothing reads it before
-    ``zero_grad``).  After a taken step ``.grad`` holds the unscaled, clipped gradient.  From the first step that meets a scaler
-    the step counts live on the device (uploaded once from the host's) and ``state_dict()`` reads them back.
+    ``zero_grad``).  After a taken step ``.grad`` holds the unscaled, clipped gradient.
+
+    The step count of every tensor lives on the device, where a skipped step is decided: ``state_dict()`` reads the counts back and
+    may wait; ``step()`` and ``zero_grad()`` never do.  A parameter whose state was dropped (``del optimizer.state[p]``) gets fresh
+    state at the next step and counts from 1 again, as in torch.
 
     Not supported (NotImplementedError): ``amsgrad``, ``maximize``, a ``closure``, parameters other than float32;
     RuntimeError: host tensors, non-contiguous parameters or gradients, parameters on several devices."""
@@ -419,7 +379,7 @@ class FullModelClipAdamW(_AdamFamily):
         # the keys of torch.optim.AdamW's own groups, so that a state dict of either loads into the other and then steps
         defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)
         defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
-        self._setup(max_norm, device_counts=False)
+        self._setup(max_norm)
         super().__init__(params, defaults)
 
 
@@ -442,7 +402,7 @@ class Adam(_AdamFamily):
         self._check_args(lr, betas, eps, weight_decay, amsgrad, maximize)
         defaults = dict(torch.optim.Adam([torch.zeros(1)]).defaults)
         defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False)
-        self._setup(max_norm, device_counts=True)
+        self._setup(max_norm)
         super().__init__(params, defaults)
 
 
@@ -478,7 +438,7 @@ class SGD(_TableOptimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(torch.optim.SGD([torch.zeros(1)], lr=1e-3).defaults)
         defaults.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False)
-        self._setup(max_norm, device_counts=True)
+        self._setup(max_norm)
         super().__init__(params, defaults)
 
     def _group_rows(self, key):
